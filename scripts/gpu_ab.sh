@@ -7,7 +7,7 @@ W=${WORKLOAD:-c2}
 for i in 1 2 3; do
   for v in "$@" new; do
     if [ $v = new ]; then unset PQP_HIP_LIBRARY; else export PQP_HIP_LIBRARY=$v; fi
-    timeout 300 python bench.py --workload $W --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline --mpc-steps 0 2>/dev/null | python -c "
+    timeout 300 python bench.py --workload $W --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline --mpc-steps 0 --full 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -10,7 +10,7 @@ mkdir -p $R/gpurun_out
 : > $O
 one() {
   local lib=$1 batch=$2
-  PQP_HIP_LIBRARY=$lib timeout 300 python bench.py --workload ${WORKLOAD:-c2} --batch $batch --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline --mpc-steps 0 2>/dev/null | python -c "
+  PQP_HIP_LIBRARY=$lib timeout 300 python bench.py --workload ${WORKLOAD:-c2} --batch $batch --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline --mpc-steps 0 --full 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -5,9 +5,9 @@ mkdir -p gpurun_out/r5c
 O=gpurun_out/r5c
 python scripts/gpu_box_probe.py c2 c5 c4 c1 2>&1 | grep BOX
 timeout 1500 python -m pytest tests -m gpu -x -q -p no:cacheprovider 2>&1 | tail -12 | tee $O/gputest_tail.txt
-timeout 400 python bench.py > $O/bench_c2.json 2> $O/bench_c2.err; echo "c2 rc=$?"
-for w in c1 c5 c5box; do timeout 300 python bench.py --workload $w --steps 10 --warmup 2 > $O/bench_$w.json 2> $O/bench_$w.err; echo "$w rc=$?"; done
-timeout 400 python bench.py --gpus 4 --inprocess --steps 5 --warmup 1 --no-cpu-baseline > $O/bench_inprocess4.json 2> $O/bench_inprocess4.err; echo "inproc rc=$?"
+timeout 400 python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; echo "c2 rc=$?"
+for w in c1 c5 c5box; do timeout 300 python bench.py --workload $w --steps 10 --warmup 2 --full > $O/bench_$w.json 2> $O/bench_$w.err; echo "$w rc=$?"; done
+timeout 400 python bench.py --gpus 4 --inprocess --steps 5 --warmup 1 --no-cpu-baseline --full > $O/bench_inprocess4.json 2> $O/bench_inprocess4.err; echo "inproc rc=$?"
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob("gpurun_out/r5c/bench_*.json")):

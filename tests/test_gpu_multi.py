@@ -54,7 +54,7 @@ def test_bench_inprocess_mode():
     """bench.py --gpus 2 --inprocess (shards on device 0): one JSON line, every QP solved, sharded == single handle"""
     env = dict(os.environ, PQP_BENCH_ONE_DEVICE="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--inprocess", "--batch", "256",
-                        "--steps", "2", "--warmup", "1"], capture_output=True, text=True, env=env, timeout=600)
+                        "--steps", "2", "--warmup", "1", "--full"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["unsolved"] == 0 and line["max_kkt_residual"] <= 1e-9

@@ -19,7 +19,7 @@ def test_two_ranks_on_one_device(extra):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "256", "--no-cpu-baseline", "--mpc-steps", "0"] + extra
+           "--batch", "256", "--no-cpu-baseline", "--mpc-steps", "0", "--full"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -41,7 +41,7 @@ def test_rccl_single_rank():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "PQP_BENCH_BACKEND", "PQP_BENCH_ONE_DEVICE"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rccl-single-rank", "--steps", "2", "--warmup", "1",
-           "--batch", "256", "--no-cpu-baseline", "--mpc-steps", "0"]
+           "--batch", "256", "--no-cpu-baseline", "--mpc-steps", "0", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

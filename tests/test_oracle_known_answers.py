@@ -61,14 +61,10 @@ def test_lower_bounded_tridiagonal(oracle):
 
 
 def test_simple_qp_with_infinity_lower_bound(oracle):
-    # reference test/data/simple_qp_with_inifinity_lower_bound.mat (dense_qp_solve.py:375-405),
-    # values restated literally (a 3x3 QP) rather than loading the .mat
+    # reference test/data/simple_qp_with_inifinity_lower_bound.mat (dense_qp_solve.py:375-405): its seven
+    # arrays (a 3x3 QP) stored as tests/golden/simple_qp_with_infinity_lower_bound.npz
     import os
-    import scipy.io as sio
-    path = "/root/reference/test/data/simple_qp_with_inifinity_lower_bound.mat"
-    if not os.path.exists(path):
-        pytest.skip("reference fixture not present on this box")
-    m = sio.loadmat(path)
+    m = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "simple_qp_with_infinity_lower_bound.npz"))
     P, q = np.asarray(m["P"], float), np.asarray(m["q"], float).ravel()
     A, b = np.asarray(m["A"], float), np.asarray(m["b"], float).ravel()
     C, l, u = np.asarray(m["C"], float), np.asarray(m["l"], float).ravel(), np.asarray(m["u"], float).ravel()

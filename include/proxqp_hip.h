@@ -209,6 +209,34 @@ int pqp_batch_get_scaled(pqp_batch* h, int64_t idx, double* H, double* g, double
 int pqp_batch_get_schur_factor(pqp_batch* h, int64_t idx, double* WS, double* dS, double* G, int32_t* slots,
                                int64_t* meta, double* mus);
 
+/* Diagnostic accessor (tests): the primal block of QP `idx` as the last solve left it in HBM.  Any output may be
+ * NULL.  All matrices row-major.  meta = {factor_valid, diagonal-structure mode (0 / 1), resolved dense backend,
+ * hessian type}, *rho = the rho the block was factorised with, i_scaled [dim] = the equilibrated unit box rows
+ * (diag(i_scaled) is the box part of the constraint matrix; all ones without box constraints).  With
+ * B = [A_s; C_s; diag(i_scaled)] (nd = n_eq + n_in (+ dim) rows, constraint id order) the buffers hold:
+ *
+ *  - dense Hessian, PrimalDualLDLT engine (setup_factorization: H_s + rho I = L D L^T):
+ *      dF [dim]        D;
+ *      F  [dim*dim]    the factor, both mirrors: F[j][j] = d_j; outside the 16 x 16 diagonal blocks F[i][j] =
+ *                      F[j][i] = L_ij (i > j); inside diagonal block b the strict triangles hold inv(L_bb) and its
+ *                      transpose (the form the triangular inverse consumes), not L_bb itself;
+ *      WL, WU [dim*dim] W = L^{-1} (lower, unit diagonal, zeros above it stored) and W^T;
+ *      Zr [nd*dim]     Z = B W^T, row c = L^{-1} b_c;   Zc [dim*nd] = Zr^T;
+ *      G (pqp_batch_get_schur_factor) [nd*nd] = Zr diag(1/D) Zr^T.
+ *  - diagonal / zero Hessian with general constraints (L = I): dF = diag(H_s) + rho (zero Hessian: rho), Zr = B,
+ *    Zc = B^T, G = B diag(1/D) B^T; F, WL, WU are not written.
+ *  - diagonal-structure mode (H diagonal / zero, no equality, every inequality row on one variable): dF as above;
+ *    the first nd entries of Zr hold zd[c] = the one entry of constraint row c (diag(C_s) for c < n_in, i_scaled
+ *    behind them), the first nd entries of G hold gd[c] = zd[c]^2 / D_col(c); the first dim entries of F hold
+ *    diag(H_s); nothing else is written.  (The one-wavefront form of this solver keeps all of it in registers.)
+ *  - PrimalLDLT engine: P_J = H_s + rho I + A_s^T A_s / mu_eq + C_J^T C_J / mu_in (J = the active list, box rows add
+ *    i_k^2 / mu_in on the diagonal) = L D L^T is kept as WL = W = L^{-1} (lower, unit diagonal; strict upper
+ *    unspecified) and dF = D, edited in place by rank-1 updates as the active set moves (ls_edited of
+ *    pqp_batch_get_schur_factor; its slot list is the active list and mus the (mu_eq, mu_in) of the factor);
+ *    WU = A_s^T A_s; F = the last assembled P_J (dim <= 112) or its blocked factor; Zr, Zc, G are not written. */
+int pqp_batch_get_primal_factor(pqp_batch* h, int64_t idx, double* F, double* dF, double* WL, double* WU,
+                                double* Zr, double* Zc, int64_t* meta, double* rho, double* i_scaled);
+
 /* per-QP device statistics of the last solve: [B][PQP_STATS_COUNT] int64
  * (cycles per phase and event counters, see proxsuite_amd/csrc/pqp_solver.hpp ST_*) */
 int pqp_batch_get_stats(pqp_batch* h, int64_t* stats);

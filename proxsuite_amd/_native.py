@@ -53,7 +53,7 @@ class NativeLib:
                "pqp_batch_update", "pqp_batch_warm_start", "pqp_batch_cleanup", "pqp_batch_reset_qp", "pqp_batch_flush",
                "pqp_batch_solve", "pqp_batch_solve_range", "pqp_batch_solve_subset", "pqp_batch_copy_qp", "pqp_batch_set_stream", "pqp_batch_set_schedule", "pqp_batch_backward", "pqp_batch_backward_range",
                "pqp_batch_get_backward", "pqp_batch_get_results", "pqp_batch_result_device_ptrs", "pqp_batch_pack_results",
-               "pqp_batch_get_scaled", "pqp_batch_get_schur_factor", "pqp_batch_get_stats", "pqp_batch_get_trace", "pqp_batch_last_solve_ms", "pqp_batch_last_prologue_ms",
+               "pqp_batch_get_scaled", "pqp_batch_get_schur_factor", "pqp_batch_get_primal_factor", "pqp_batch_get_stats", "pqp_batch_get_trace", "pqp_batch_last_solve_ms", "pqp_batch_last_prologue_ms",
                "pqp_batch_launch_config", "pqp_batch_solve_async", "pqp_batch_solve_range_async",
                "pqp_batch_solve_subset_async", "pqp_batch_wait", "pqp_batch_enable_host_results",
                "pqp_batch_host_results", "pqp_batch_host_results_fresh", "pqp_batch_own_stream", "pqp_batch_backward_subset",
@@ -103,6 +103,7 @@ class NativeLib:
         L.pqp_batch_get_stats.argtypes = [vp, C.POINTER(C.c_int64)]
         L.pqp_batch_get_trace.argtypes = [vp, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         L.pqp_batch_get_schur_factor.argtypes = [vp, C.c_int64] + [_DP] * 3 + [C.POINTER(C.c_int32), C.POINTER(C.c_int64), _DP]
+        L.pqp_batch_get_primal_factor.argtypes = [vp, C.c_int64] + [_DP] * 6 + [C.POINTER(C.c_int64), _DP, _DP]
         L.pqp_batch_last_solve_ms.argtypes = [vp]
         L.pqp_batch_last_solve_ms.restype = C.c_double
         L.pqp_batch_last_prologue_ms.argtypes = [vp]
@@ -503,6 +504,21 @@ class Batch:
             self._h, idx, WS.ctypes.data_as(_DP), dS.ctypes.data_as(_DP), G.ctypes.data_as(_DP),
             slots.ctypes.data_as(C.POINTER(C.c_int32)), meta.ctypes.data_as(C.POINTER(C.c_int64)), mus.ctypes.data_as(_DP)))
         return WS, dS, G, slots[:nc], dict(zip(("n_slots", "n_c", "ls_valid", "ls_edited"), meta.tolist())), mus
+
+    def primal_factor(self, idx):
+        """diagnostic: the primal block of QP `idx` after its last solve as a dict -- F, dF, WL, WU, Zr, Zc, i_scaled,
+        rho and meta (factor_valid, diag_mode, backend, hessian); what each array holds: include/proxqp_hip.h"""
+        n, nd = self.n, self.n_eq + self.n_c
+        out = dict(F=np.zeros((n, n)), dF=np.zeros(n), WL=np.zeros((n, n)), WU=np.zeros((n, n)), Zr=np.zeros((nd, n)),
+                   Zc=np.zeros((n, nd)), i_scaled=np.zeros(n))
+        meta, rho = np.zeros(4, dtype=np.int64), C.c_double(0)
+        p = lambda a: a.ctypes.data_as(_DP)
+        self.lib.check(self.lib.L.pqp_batch_get_primal_factor(
+            self._h, int(idx), p(out["F"]), p(out["dF"]), p(out["WL"]), p(out["WU"]), p(out["Zr"]), p(out["Zc"]),
+            meta.ctypes.data_as(C.POINTER(C.c_int64)), C.cast(C.byref(rho), _DP), p(out["i_scaled"])))
+        out["rho"] = rho.value
+        out["meta"] = dict(zip(("factor_valid", "diag_mode", "backend", "hessian"), meta.tolist()))
+        return out
 
     def stats(self):
         a = np.zeros((self.B, PQP_STATS_COUNT), dtype=np.int64)

@@ -1428,6 +1428,44 @@ pqp_batch_get_schur_factor(pqp_batch* h, int64_t idx, double* WS, double* dS, do
   return PQP_OK;
 }
 
+// Diagnostic: the primal block of QP `idx` as the last solve left it in HBM (layouts: include/proxqp_hip.h).  The
+// tests judge every stage of setup_factorization against its own inputs: the LDL^T of H_s + rho I, the explicit
+// inverse W = L^{-1}, Z = B W^T and the Gram matrix G (pqp_batch_get_schur_factor hands out G) -- or, with the
+// PrimalLDLT engine, the pair (W, D) of P_J.
+int
+pqp_batch_get_primal_factor(pqp_batch* h, int64_t idx, double* F, double* dF, double* WL, double* WU, double* Zr,
+                            double* Zc, int64_t* meta, double* rho, double* i_scaled)
+{
+  if (int rc = check_idx(h, idx))
+    return rc;
+  if (idx < 0)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "pqp_batch_get_primal_factor addresses one QP");
+  if (int rc = settle(h))
+    return rc;
+  PQP_ON_DEVICE(h->device);
+  const pqp::Dims& d = h->dev.d;
+  const pqp::Batch& D = h->dev;
+  const size_t n = size_t(d.n), nd = size_t(d.nd);
+  int rc = 0;
+  if ((rc = copy_out(F, D.F, idx, D.B, n * n)) || (rc = copy_out(dF, D.dF, idx, D.B, n)) ||
+      (rc = copy_out(WL, D.WL, idx, D.B, n * n)) || (rc = copy_out(WU, D.WU, idx, D.B, n * n)) ||
+      (rc = copy_out(Zr, D.Zr, idx, D.B, nd * n)) || (rc = copy_out(Zc, D.Zc, idx, D.B, n * nd)) ||
+      (rc = copy_out(i_scaled, D.is, idx, D.B, n)))
+    return rc;
+  pqp::State s;
+  HIP_TRY(hipMemcpy(&s, D.state + idx, sizeof(s), hipMemcpyDefault));
+  if (meta) {
+    meta[0] = s.factor_valid;
+    // (Solver::set_diag_mode: the signature of the batch and the per-QP structure of C found by init / update)
+    meta[1] = (pqp::diag_structure_signature(d.hessian, d.n_eq, d.n_in, d.box) && s.c_diag != 0) ? 1 : 0;
+    meta[2] = d.backend;
+    meta[3] = d.hessian;
+  }
+  if (rho)
+    *rho = s.rho_fact;
+  return PQP_OK;
+}
+
 int
 pqp_batch_get_stats(pqp_batch* h, int64_t* stats)
 {

@@ -148,8 +148,9 @@ def build_hip(force: bool = False, extra_flags=(), out: Path = None, tus=KERNEL_
     # sixteen kernel families)
     common = hip_headers() + [Path(__file__)]
     own = {"capi.o": "pqp_capi.hip", "multi.o": "pqp_multi.hip", "calib.o": "pqp_calib.hip"}
-    # (pqp_dwave.hpp is parsed by every kernel family and instantiated by family 17 alone: inline templates, no code elsewhere)
-    only = {"pqp_dwave.hpp": ("kernels_17.o",)}
+    # (pqp_dwave.hpp is parsed by every kernel family; family 17 instantiates its kernel, and family 6 compiles the host
+    # side of its dispatch -- pqp_dense_wave_dispatch / pqp_dense_wave_lds_bytes: inline templates, no code elsewhere)
+    only = {"pqp_dwave.hpp": ("kernels_17.o", "kernels_6.o")}
     def deps_of(o):
         return [h for h in common if h.name not in only or o.name in only[h.name]] + [CSRC / own.get(o.name, "pqp_kernels.hip")]
     todo = [j for j in jobs if force or not _newer(j[1], deps_of(j[1]))]

@@ -1365,6 +1365,12 @@ struct DiagSolver
       dF[c] = 1.0;
       dS[c] = 1.0;
     }
+    {
+      // State::primal_valid for the epilogue (this kernel's primal block is a few values per lane: always rebuilt under
+      // do_factor, never skipped)
+      const bool primal_kept = W.primal_valid != 0 && W.rho_fact == info.rho && !(do_rescale && W.scaled_valid == 0);
+      W.primal_valid = (do_factor || primal_kept) ? 1 : 0;
+    }
     if (do_factor) {
       toc(ST_CYC_F_LOAD);
       factor_primal_block();
@@ -1695,7 +1701,7 @@ struct DiagSolver
       W.ls_edited = 0;
       W.mu_eq_fact = info.mu_eq;
       W.mu_in_fact = info.mu_in;
-      W.rho_fact = info.rho;
+      W.rho_fact = info.rho; // (W.primal_valid: set beside the factorisation)
       *P.state() = W;
       PQP_GLOBAL long long* gs_ = P.stats();
 #ifdef PQP_STATS

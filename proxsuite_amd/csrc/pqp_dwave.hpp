@@ -2506,6 +2506,12 @@ struct DWave
       }
     }
     vload(dF, P.dF(), n, 1.0);
+    {
+      // State::primal_valid for the epilogue, from the state and the rho Solver::prologue decided on: the block in HBM is
+      // the one it has just factorised (do_factor) or the one it found valid at this rho
+      const bool primal_kept = W.primal_valid != 0 && W.rho_fact == info.rho && !(dirty && !wswpr && W.scaled_valid == 0);
+      W.primal_valid = (do_factor || primal_kept) ? 1 : 0;
+    }
     if (do_factor) {
       n_c = 0;
       n_slots = 0;
@@ -2892,7 +2898,7 @@ struct DWave
       W.ls_edited = schur_incremental ? 1 : 0;
       W.mu_eq_fact = info.mu_eq;
       W.mu_in_fact = info.mu_in;
-      W.rho_fact = info.rho;
+      W.rho_fact = info.rho; // (W.primal_valid: set where the solve starts)
       *P.state() = W;
       PQP_GLOBAL long long* gs_ = P.stats();
 #ifdef PQP_STATS

@@ -563,6 +563,12 @@ pqp_launch_solve(pqp_batch* h)
   const bool common = h->dev.d.box == 0 && h->dev.d.hessian == PQP_HESSIAN_DENSE &&
                       h->dev.d.backend != PQP_BACKEND_PRIMAL_LDLT;
   h->prologue_timed = false;
+  {
+    // PQP_PRIMAL_REUSE=0: every solve factorises its primal block as if State::primal_valid did not exist (the A/B
+    // partner of the tests and of the measurements; read per launch, like PQP_DENSE_KERNEL)
+    const char* e = std::getenv("PQP_PRIMAL_REUSE");
+    h->dev.primal_reuse = (e && e[0] == '0') ? 0 : 1;
+  }
   if (h->vec_scratch) // per-QP vectors beyond the LDS of a CU: the solver runs on an HBM slice per workgroup
     return pqp_launch_solve_hbm(h, common);
   switch (h->nt) {

@@ -156,7 +156,25 @@ struct State
   int c_diag;       // C has no off-diagonal entry and n_in == dim (e.g. bounds passed as C = I): set by init / update
   int ls_edited;    // that factor has taken rank-1 edits since its last full factorisation (refinement fallback, solver.hpp:474-532)
   int scaled_valid; // H_s, A_s, C_s (both orientations) in HBM are the equilibrated model: written by init / update, read-only afterwards
-  int _pad2;
+  // F, dF, WL, WU, Zr, Zc, G in HBM are the PrimalDualLDLT primal block of the CURRENT H_s, A_s, C_s at rho = rho_fact: a
+  // solve whose rho is that same double skips factor_primal_block (Batch::primal_reuse).  Unlike factor_valid it outlives
+  // work_cleanup_flags: the block is a function of (scaled matrices, rho) alone, not of vectors, mu, iterate or active set.
+  // Every writer of those arrays or of Hs / As / ATs / Cs / CTs, and what it does to the flag:
+  //   setup_body, CMD_INIT / !is_initialized / matrices_given / re-run Ruiz   rewrites the scaled matrices   -> 0
+  //   setup_body, vector-only update on the stored scaling                    writes no matrix (diagonal structure: the
+  //                                                                           same compact diagonals again)  -> kept
+  //   setup_body, CMD_CLEANUP                                                 writes none of them            -> kept
+  //   solve / prologue / diagonal kernel, rescale with rewrite_matrices       rewrites the scaled matrices   -> 0 before
+  //                                                                           the decision (always factorises)
+  //   factor_primal_block + build_ZG, engine pm() == false (Solver::solve, Solver::prologue in front of the one-wavefront
+  //     kernel, the diagonal kernel's own)                                    the block at info.rho          -> 1, rho_fact
+  //   a solve that restores (WARM_START_WITH_PREVIOUS_RESULT, do_factor false) writes none                   -> kept if
+  //                                                                           rho_fact == info.rho, else 0
+  //   PrimalLDLT solves (pm()): P_J in F, A_s^T A_s in WU, W of P_J in WL, its D in dF                      -> 0
+  //   Solver::backward: the block at rho_new                                                                 -> 0
+  //   pqp_batch_copy_qp: every per-QP array and this record travel together                                  -> carried
+  // The iteration code (Schur edits, KKT solves, refinement) only reads the seven arrays.
+  int primal_valid;
   double ruiz_c;
   double dual_feasibility_rhs_2;
   double correction_guess_rhs_g;
@@ -250,6 +268,9 @@ struct Batch
   double* trace;
   const int* trace_slot;
   int trace_cap;
+  // a solve may skip the primal block that State::primal_valid vouches for.  Set per launch by the host from
+  // PQP_PRIMAL_REUSE (unset / 1: on; 0: factorise as if the flag did not exist -- the A/B partner of the tests)
+  int primal_reuse;
 };
 
 // QPLayer backward (reference dense/compute_ECJ.hpp): inputs and outputs of one launch.
@@ -990,8 +1011,13 @@ setup_body(const Batch& batch, long q, lptr lds_base)
 
   const bool is_init = (cmd.op == CMD_INIT) || !W.is_initialized; // wrapper.hpp:743-746
   const long long setup_t0 = wall_clock64();                      // wrapper.hpp:374-377
+  // a vector-only update on the stored scaling (c, delta) would rewrite H_s, A_s, A_s^T, C_s, C_s^T with the bits they
+  // hold: the matrices stay as they are, and with them the primal block a solve left behind (State::primal_valid)
+  const bool keep_matrices = !is_init && !cmd.matrices_given && !cmd.preconditioner && W.scaled_valid != 0;
   __syncthreads();
   if (threadIdx.x == 0) {
+    if (!keep_matrices)
+      W.primal_valid = 0;
     if (is_init) {
       W.refactorize = (st.initial_guess == PQP_WARM_START_WITH_PREVIOUS_RESULT) ? 1 : 0;
       W.proximal_parameter_update = 0;
@@ -1088,7 +1114,7 @@ setup_body(const Batch& batch, long q, lptr lds_base)
       S[k] = P.delta()[k];
     __syncthreads();
   }
-  write_scaled<NT, true>(batch, q, S, c, true, false, true, red + (2 * RED_VALS * (NT / WAVE) + 16));
+  write_scaled<NT, true>(batch, q, S, c, true, false, !keep_matrices, red + (2 * RED_VALS * (NT / WAVE) + 16));
   {
     // structure detection for the diagonal fast path of the solve kernel (Solver::dm): no
     // off-diagonal entry in C with n_in == dim (bounds handed over as C = I, reference
@@ -4176,10 +4202,17 @@ struct Solver
       const bool rewrite_matrices = W.scaled_valid == 0; // (never after an init / update: see write_scaled)
       write_scaled<NT>(batch, q, S, ruiz_c, false, dm(), rewrite_matrices);
       // H, A, C read; H_s, A_s, A_s^T, C_s, C_s^T written (diagonal structure: the two diagonals)
-      if (rewrite_matrices)
+      if (rewrite_matrices) {
         bytes(dm() ? ((long)n * 3 + (long)ni * 3) * 8 : ((long)n * n * 2 + 3L * ne * n + 3L * ni * n) * 8);
+        W.primal_valid = 0;
+      }
       toc(ST_CYC_SCALE);
     }
+    // the primal block in HBM is this solve's already (State::primal_valid): same scaled matrices, and rho -- fixed for
+    // the whole solve by the cold_start above or by the set-up kernel -- is the double it was factorised at (a NaN or a
+    // changed default_rho compares unequal and factorises)
+    const bool primal_kept = !pm() && W.primal_valid != 0 && W.rho_fact == info.rho;
+    W.primal_valid = (!pm() && (do_factor || primal_kept)) ? 1 : 0; // what the epilogue stores
     if constexpr (!LATE_LOADS) {
       vload(L.gs(), P.gs(), n);
       vload(L.bs(), P.bs(), ne);
@@ -4195,17 +4228,19 @@ struct Solver
         scale_warm_start();
     }
     if (do_factor) {
+      if (!(batch.primal_reuse && primal_kept)) {
 #ifdef PQP_STATS
-      if (threadIdx.x == 0)
-        L.stat()[ST_CYC_FACTOR_H] -= clock64();
+        if (threadIdx.x == 0)
+          L.stat()[ST_CYC_FACTOR_H] -= clock64();
 #endif
-      tic();
-      for (int rp = 0; rp < reps(6); ++rp)
-        factor_primal_block();
+        tic();
+        for (int rp = 0; rp < reps(6); ++rp)
+          factor_primal_block();
 #ifdef PQP_STATS
-      if (threadIdx.x == 0)
-        L.stat()[ST_CYC_FACTOR_H] += clock64();
+        if (threadIdx.x == 0)
+          L.stat()[ST_CYC_FACTOR_H] += clock64();
 #endif
+      }
       tic();
       n_c = 0;
       n_slots = 0;
@@ -4235,6 +4270,14 @@ struct Solver
       __syncthreads();
       if (do_scale_ws)
         scale_warm_start();
+    }
+    if (do_factor && batch.primal_reuse && primal_kept) {
+      // the factorisation was skipped.  factor_primal_block + build_ZG leave one thing outside HBM: D in L.dF (t1 = 1 / D,
+      // the staging area and L.top() are scratch of theirs that nothing reads afterwards); nothing above reads it.
+      // (Reloaded HERE and not in an else branch of the factorisation: that form moved the register allocation of the
+      // general 512- / 1024-thread kernels by 18 - 20 spilled registers, this one by 2)
+      vload(L.dF(), P.dF(), n);
+      __syncthreads();
     }
     if (do_restore) {
       // WARM_START_WITH_PREVIOUS_RESULT on an unchanged model: reuse the block
@@ -4657,7 +4700,7 @@ struct Solver
       W.ls_edited = schur_incremental ? 1 : 0;
       W.mu_eq_fact = info.mu_eq;
       W.mu_in_fact = info.mu_in;
-      W.rho_fact = info.rho;
+      W.rho_fact = info.rho; // (W.primal_valid: decided beside the factorisation above)
       *P.state() = W;
       L.stat()[ST_N_ACTIVE_FINAL] = n_c;
       L.stat()[ST_CYC_TOTAL] += clock64();
@@ -4671,8 +4714,9 @@ struct Solver
   // dirty re-solve (solver.hpp:1192-1214) and setup_factorization (H_s + rho I = L D L^T, W = L^{-1}, Z, G) for the
   // QPs whose solve will need them, decided exactly as solve() decides (same state, same settings; nothing of the
   // state is written).  The one-wavefront dense kernel (pqp_dwave.hpp) runs behind it and starts from what it leaves
-  // in HBM (F, dF, WL, WU, Zr, Zc, G and the equilibrated vectors): the GEMM-shaped, once-per-solve part of a solve
-  // keeps its 256-thread form and its own register budget, the iteration gets a kernel of its own.
+  // in HBM (F, dF, WL, WU, Zr, Zc, G and the equilibrated vectors): the GEMM-shaped, once-per-(matrices, rho) part of a
+  // solve keeps its 256-thread form and its own register budget, the iteration gets a kernel of its own.  On a re-solve
+  // of an unchanged model (State::primal_valid) only the vectors are left to do; the kernel is launched all the same.
   __device__ __forceinline__ void prologue()
   {
     const int ne = d.n_eq;
@@ -4705,7 +4749,9 @@ struct Solver
         bytes(((long)d.n * d.n * 2 + 3L * ne * d.n + 3L * d.n_in * d.n) * 8);
       toc(ST_CYC_SCALE);
     }
-    if (do_factor) {
+    // (as solve() decides: the block in HBM is this solve's already -- State::primal_valid; rho was fixed above)
+    const bool primal_kept = !pm() && W.primal_valid != 0 && W.rho_fact == info.rho && !(do_rescale && W.scaled_valid == 0);
+    if (do_factor && !(batch.primal_reuse && primal_kept)) {
       tic();
       factor_primal_block();
       toc(ST_CYC_FACTOR_H);
@@ -4874,6 +4920,7 @@ struct Solver
       info.store(*P.info());
       State& Ww = *P.state();
       Ww.factor_valid = 0;
+      Ww.primal_valid = 0; // (the block in HBM was factorised at rho_new)
       Ww.ls_valid = 0;
       Ww.dirty = 1;
     }

@@ -259,8 +259,14 @@ double pqp_batch_last_solve_ms(const pqp_batch* h);
  * iteration kernel behind it, csrc/pqp_dwave.hpp): the part of pqp_batch_last_solve_ms the prologue kernel took, 0 for a
  * launch of one kernel.  (No counterpart in the reference: measurement only.) */
 double pqp_batch_last_prologue_ms(const pqp_batch* h);
-/* bytes of dynamic LDS and threads per workgroup chosen for this batch */
+/* threads per workgroup and bytes of per-QP vector workspace (dynamic LDS) of the kernel a launch of the WHOLE batch
+ * would run on now (the library picks the kernel per launch, from the shape, the number of QPs of the launch and the
+ * device) */
 int pqp_batch_launch_config(const pqp_batch* h, int* threads, int64_t* lds_bytes);
+/* The iteration kernel the last solve launch of the handle ran on, spelled as the build's kernel-resource record spells
+ * it ("pqp_solve_kernel<256,4,1>", "pqp_diag_kernel<2,2>", "pqp_dwave_kernel<2>", "pqp_solve_hbm_kernel<1024,4,0>");
+ * "" before the first solve.  The string belongs to the library.  (No counterpart in the reference: measurement only.) */
+const char* pqp_batch_last_kernel(const pqp_batch* h);
 
 /* ------------------------------------------------------------------------------------------------------------
  * One batch over several GPUs of the node, in ONE process (SURVEY 8(b) `device_mask`, 7 step 7; reference

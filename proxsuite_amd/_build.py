@@ -122,13 +122,40 @@ def flags_tag(extra_flags) -> str:
     return "v" + hashlib.sha1(" ".join(extra_flags).encode()).hexdigest()[:8]
 
 
+def hipcc() -> str:
+    return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+HOST_OBJECTS = {"capi.o": "pqp_capi.hip", "multi.o": "pqp_multi.hip", "calib.o": "pqp_calib.hip"}
+
+
+def hip_objects(odir: Path, tus=KERNEL_TUS):
+    """the objects libproxqp_hip.so is linked from: the host translation units and one per kernel family"""
+    return [odir / o for o in HOST_OBJECTS] + [odir / ("kernels_%d.o" % k) for k in tus]
+
+
+def compile_tu(k: int, obj: Path, extra_flags=()):
+    """kernel family `k` of pqp_kernels.hip -> `obj`; returns the finished process (stderr: the resource remarks)"""
+    return _run([hipcc(), *hip_flags(extra_flags), *TU_FLAGS.get(k, []), "-DPQP_TU=%d" % k, "-c",
+                 str(CSRC / "pqp_kernels.hip"), "-o", str(obj)])
+
+
+def link_hip(lib: Path, odir: Path = None, replaced=None, tus=KERNEL_TUS) -> Path:
+    """`lib` <- the objects of the build in `odir` (default: the product's), those named in `replaced`
+    ({object name: another object}) swapped: how a variant that differs in one kernel family is made in seconds"""
+    odir, replaced = odir or OBJ_DIR / "default", replaced or {}
+    Path(lib).parent.mkdir(parents=True, exist_ok=True)
+    _run([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(lib),
+          *[str(replaced.get(o.name, o)) for o in hip_objects(odir, tus)]])
+    return Path(lib)
+
+
 def build_hip(force: bool = False, extra_flags=(), out: Path = None, tus=KERNEL_TUS) -> Path:
     """Cross-compiles for gfx950 (works without a GPU).  `out` / `extra_flags` build a variant
     of the library somewhere else (A/B runs: scripts/gpu_ab.sh); `tus` restricts the kernel
     families that are compiled (development only: the launchers of the others are then missing
     and the link fails unless the variant is never asked for them... so keep the default)."""
     from concurrent.futures import ThreadPoolExecutor
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     lib = Path(out) if out else HIP_LIB
     deps = list(hip_sources()) + hip_headers() + [Path(__file__)]
     if not force and _newer(lib, deps):
@@ -136,35 +163,30 @@ def build_hip(force: bool = False, extra_flags=(), out: Path = None, tus=KERNEL_
     tag = "default" if not extra_flags else flags_tag(extra_flags)
     odir = OBJ_DIR / tag
     odir.mkdir(parents=True, exist_ok=True)
-    flags = hip_flags(extra_flags)
-    jobs = [([hipcc, *flags, "-c", str(CSRC / "pqp_capi.hip"), "-o", str(odir / "capi.o")], odir / "capi.o"),
-            ([hipcc, *flags, "-c", str(CSRC / "pqp_multi.hip"), "-o", str(odir / "multi.o")], odir / "multi.o"),
-            ([hipcc, *flags, "-c", str(CSRC / "pqp_calib.hip"), "-o", str(odir / "calib.o")], odir / "calib.o")]
-    for k in tus:
-        o = odir / ("kernels_%d.o" % k)
-        jobs.append(([hipcc, *flags, *TU_FLAGS.get(k, []), "-DPQP_TU=%d" % k, "-c", str(CSRC / "pqp_kernels.hip"),
-                      "-o", str(o)], o))
     # an object is stale when ITS source, a header or this recipe is newer (an edit of pqp_multi.hip does not recompile
     # sixteen kernel families)
     common = hip_headers() + [Path(__file__)]
-    own = {"capi.o": "pqp_capi.hip", "multi.o": "pqp_multi.hip", "calib.o": "pqp_calib.hip"}
     # (pqp_dwave.hpp is parsed by every kernel family; family 17 instantiates its kernel, and family 6 compiles the host
-    # side of its dispatch -- pqp_dense_wave_dispatch / pqp_dense_wave_lds_bytes: inline templates, no code elsewhere)
+    # side of its dispatch -- pqp_plan_solve reads dwave_signature / dwave_lds_bytes: inline templates, no code elsewhere)
     only = {"pqp_dwave.hpp": ("kernels_17.o", "kernels_6.o")}
     def deps_of(o):
-        return [h for h in common if h.name not in only or o.name in only[h.name]] + [CSRC / own.get(o.name, "pqp_kernels.hip")]
-    todo = [j for j in jobs if force or not _newer(j[1], deps_of(j[1]))]
+        return [h for h in common if h.name not in only or o.name in only[h.name]] + [CSRC / HOST_OBJECTS.get(o.name, "pqp_kernels.hip")]
+    def compile_object(o):
+        if o.name in HOST_OBJECTS:
+            return _run([hipcc(), *hip_flags(extra_flags), "-c", str(CSRC / HOST_OBJECTS[o.name]), "-o", str(o)])
+        return compile_tu(int(o.stem.split("_")[1]), o, extra_flags)
+    todo = [o for o in hip_objects(odir, tus) if force or not _newer(o, deps_of(o))]
     with ThreadPoolExecutor(max_workers=max(1, min(len(todo), os.cpu_count() or 1))) as ex:
-        results = list(ex.map(lambda j: _run(j[0]), todo))
-    _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(lib), *[str(j[1]) for j in jobs]])
+        results = list(ex.map(compile_object, todo))
+    link_hip(lib, odir, tus=tus)
     # registers / spills / scratch of every kernel that was (re)compiled, merged into the record of this build tag
     import json
     rec_path = odir / "kernel_resources.json"
     rec = json.loads(rec_path.read_text()) if rec_path.exists() else {}
-    for j, r in zip(todo, results):
-        rec = {k: v for k, v in rec.items() if v.get("object") != j[1].name}  # (what that object held before this compile)
+    for o, r in zip(todo, results):
+        rec = {k: v for k, v in rec.items() if v.get("object") != o.name}  # (what that object held before this compile)
         for name, fields in parse_kernel_resources(r.stderr).items():
-            rec[kernel_label(name)] = dict(fields, object=j[1].name)
+            rec[kernel_label(name)] = dict(fields, object=o.name)
     rec_path.write_text(json.dumps(rec, indent=1, sort_keys=True))
     return lib
 
@@ -195,21 +217,15 @@ def build_hip_variants(force: bool = False):
     uses 2), for the GPU regression test that sweeps them (tests/test_gpu_parity.py): round 1 saw
     NaNs at (512, 4) with a kernel that has since been rewritten; the sweep keeps watch.  Only the
     translation unit of that kernel is recompiled; the other objects are the product's."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    VARIANT_DIR.mkdir(exist_ok=True)
     out = []
     deps = list(hip_sources()) + hip_headers() + [Path(__file__)]
     build_hip()  # the product objects the variants link against
-    base = OBJ_DIR / "default"
     for w in (3, 4):
         lib = VARIANT_DIR / ("libproxqp_hip_wps512_%d.so" % w)
         if force or not _newer(lib, deps):
-            o3 = base / ("kernels_3_wps%d.o" % w)
-            _run([hipcc, *hip_flags(("-DPQP_WPS_512=%d" % w,)), *TU_FLAGS.get(3, []), "-DPQP_TU=3", "-c",
-                  str(CSRC / "pqp_kernels.hip"),
-                  "-o", str(o3)])
-            objs = [base / "capi.o", base / "multi.o", base / "calib.o"] + [o3 if k == 3 else base / ("kernels_%d.o" % k) for k in KERNEL_TUS]
-            _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(lib), *map(str, objs)])
+            o3 = OBJ_DIR / "default" / ("kernels_3_wps%d.o" % w)
+            compile_tu(3, o3, ("-DPQP_WPS_512=%d" % w,))
+            link_hip(lib, replaced={"kernels_3.o": o3})
         out.append(lib)
     return out
 
@@ -218,22 +234,14 @@ def build_tu_variant(tu, extra_flags, out: Path):
     """A/B partner that differs from the product in ONE kernel family: translation unit `tu` recompiled with
     `extra_flags`, every other object taken from the product build (seconds instead of minutes).  Returns (library path,
     {kernel: resources})."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     build_hip()
-    base = OBJ_DIR / "default"
-    out = Path(out)
-    out.parent.mkdir(parents=True, exist_ok=True)
-    tus = [tu] if isinstance(tu, int) else list(tu)
     repl, res = {}, {}
-    for t in tus:
-        o = base / ("kernels_%d_%s.o" % (t, flags_tag(extra_flags)))
-        r = _run([hipcc, *hip_flags(tuple(extra_flags)), *TU_FLAGS.get(t, []), "-DPQP_TU=%d" % t, "-c",
-                  str(CSRC / "pqp_kernels.hip"), "-o", str(o)])
-        repl[t] = o
+    for t in ([tu] if isinstance(tu, int) else list(tu)):
+        o = OBJ_DIR / "default" / ("kernels_%d_%s.o" % (t, flags_tag(extra_flags)))
+        r = compile_tu(t, o, tuple(extra_flags))
+        repl["kernels_%d.o" % t] = o
         res.update({kernel_label(k): v for k, v in parse_kernel_resources(r.stderr).items()})
-    objs = [base / "capi.o", base / "multi.o", base / "calib.o"] + [repl.get(k, base / ("kernels_%d.o" % k)) for k in KERNEL_TUS]
-    _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(out), *map(str, objs)])
-    return out, res
+    return link_hip(out, replaced=repl), res
 
 
 def build_oracle(force: bool = False) -> Path:

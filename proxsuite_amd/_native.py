@@ -54,7 +54,7 @@ class NativeLib:
                "pqp_batch_solve", "pqp_batch_solve_range", "pqp_batch_solve_subset", "pqp_batch_copy_qp", "pqp_batch_set_stream", "pqp_batch_set_schedule", "pqp_batch_backward", "pqp_batch_backward_range",
                "pqp_batch_get_backward", "pqp_batch_get_results", "pqp_batch_result_device_ptrs", "pqp_batch_pack_results",
                "pqp_batch_get_scaled", "pqp_batch_get_schur_factor", "pqp_batch_get_primal_factor", "pqp_batch_get_stats", "pqp_batch_get_trace", "pqp_batch_last_solve_ms", "pqp_batch_last_prologue_ms",
-               "pqp_batch_launch_config", "pqp_batch_solve_async", "pqp_batch_solve_range_async",
+               "pqp_batch_launch_config", "pqp_batch_last_kernel", "pqp_batch_solve_async", "pqp_batch_solve_range_async",
                "pqp_batch_solve_subset_async", "pqp_batch_wait", "pqp_batch_enable_host_results",
                "pqp_batch_host_results", "pqp_batch_host_results_fresh", "pqp_batch_own_stream", "pqp_batch_backward_subset",
                "pqp_multi_create", "pqp_multi_destroy", "pqp_multi_size", "pqp_multi_shard_count", "pqp_multi_shard",
@@ -109,6 +109,8 @@ class NativeLib:
         L.pqp_batch_last_prologue_ms.argtypes = [vp]
         L.pqp_batch_last_prologue_ms.restype = C.c_double
         L.pqp_batch_launch_config.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+        L.pqp_batch_last_kernel.argtypes = [vp]
+        L.pqp_batch_last_kernel.restype = C.c_char_p
         L.pqp_batch_solve_async.argtypes = [vp]
         L.pqp_batch_solve_range_async.argtypes = [vp, C.c_int64, C.c_int64]
         L.pqp_batch_solve_subset_async.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64]
@@ -536,7 +538,14 @@ class Batch:
             self.lib.check(self.lib.L.pqp_batch_get_trace(self._h, int(idx), out.ctypes.data, n.value, C.byref(n)))
         return out
 
+    @property
+    def last_kernel(self):
+        """the iteration kernel the last solve launch ran on, as the build's kernel-resource record spells it
+        ("pqp_solve_kernel<256,4,1>", "pqp_dwave_kernel<2>", ...); "" before the first solve"""
+        return self.lib.L.pqp_batch_last_kernel(self._h).decode()
+
     def launch_config(self):
+        """(threads per workgroup, bytes of LDS) of the kernel a launch of the WHOLE batch would run on now"""
         t = C.c_int(0)
         b = C.c_int64(0)
         self.lib.check(self.lib.L.pqp_batch_launch_config(self._h, C.byref(t), C.byref(b)))

@@ -96,6 +96,7 @@ struct pqp_batch
   hipStream_t owned_stream = nullptr; // pqp_batch_own_stream: a non-blocking stream created for (and destroyed with) the handle
   double* vec_scratch = nullptr; // non-null: per-QP vectors live in HBM (B slices of lds_solve bytes), see pqp_kernels.hip TU 9
   long range_first = 0, range_count = 0;
+  const char* last_kernel = ""; // label of the iteration kernel of the last launch (pqp_batch_last_kernel)
   long setup_first = 0, setup_count = 0; // QPs with a queued init / update / cleanup command
   const int* subset_order = nullptr;     // pqp_batch_solve_subset: slot of workgroup i (device memory)
   const std::vector<int>* subset_host = nullptr; // ... and the same list on the host, for the duration of the launch call
@@ -149,13 +150,34 @@ struct DeviceGuard
   if (!guard_.ok())                                                                                 \
     return pqp_fail(PQP_ERR_HIP, "hipSetDevice(" + std::to_string(dev) + ") failed: the call did not run")
 
-// launchers (pqp_kernels.hip); each picks the instantiation for h->nt / the model signature
+// Every solve kernel of the library (the iteration kernel of a launch), named after the entry of the product build's
+// kernel_resources.json it stands for: <threads>_<waves per SIMD>_<SPEC>.  SPEC 1: no box, dense Hessian, PrimalDualLDLT;
+// 0: everything; 2: the diagonal-structure solver.  DIAG_<E> / DWAVE: the one-wavefront kernels of pqp_diag.hpp (E
+// register slots per vector) and pqp_dwave.hpp; HBM: per-QP vectors in HBM (1024 threads).
+enum pqp_kernel : int
+{
+  PQP_K_256_4_1, PQP_K_256_3_1, PQP_K_256_2_1, PQP_K_256_1_1, PQP_K_256_3_0, PQP_K_256_1_0, PQP_K_256_2_2,
+  PQP_K_DIAG_1, PQP_K_DIAG_2, PQP_K_DIAG_4, PQP_K_DWAVE,
+  PQP_K_512_2_1, PQP_K_512_2_0, PQP_K_512_4_1, PQP_K_512_4_0, PQP_K_1024_1, PQP_K_1024_0, PQP_K_HBM_1, PQP_K_HBM_0,
+  PQP_K_COUNT
+};
+
+// What one solve launch runs on.  `lds`: bytes of the per-QP vector workspace -- the dynamic LDS of the launch, except
+// for the HBM kernels, whose workspace is a slice of pqp_batch::vec_scratch (they take no dynamic LDS).
+struct LaunchPlan
+{
+  pqp_kernel kernel;
+  int threads;   // per workgroup
+  size_t lds;
+  bool prologue; // pqp_prologue_kernel<256> (h->lds_solve bytes of LDS) runs in front of `kernel`
+};
+
+// launchers (pqp_kernels.hip)
 int pqp_launch_setup(pqp_batch* h);
-int pqp_launch_solve(pqp_batch* h);
-int pqp_diag_wave_slots(int dim); // register slots per vector of that kernel for a dimension (1, 2 or 4)
-int pqp_diag_dispatch(const pqp_batch* h, bool whole_batch = false); // 1: the launch (or, whole_batch, a launch of every QP) goes to the one-wavefront diagonal kernel (pqp_diag.hpp)
-int pqp_dense_wave_dispatch(const pqp_batch* h, long count); // 1: a launch of `count` QPs goes to the one-wavefront dense kernel (pqp_dwave.hpp)
-size_t pqp_dense_wave_lds_bytes();
+// The kernel a launch of the QPs first .. first + count - 1 (`subset`: of those QPs, `count` of them) runs on.  Pure: it
+// enqueues nothing and leaves the handle alone; the environment switches are read per call.
+LaunchPlan pqp_plan_solve(const pqp_batch* h, long first, long count, const std::vector<int>* subset);
+int pqp_launch_solve(pqp_batch* h); // plans the launch h->range_* / h->subset_* describe, times and enqueues it
 int pqp_launch_backward(pqp_batch* h, const pqp::BackwardArgs& bw, long count);
 int pqp_launch_order(pqp_batch* h, long count);
 int pqp_launch_pack(pqp_batch* h, long first, long count, double* out, hipStream_t stream);

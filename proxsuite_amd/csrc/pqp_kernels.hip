@@ -1,22 +1,27 @@
-// The kernels of libproxqp_hip.so and their launchers.  Compiled once per kernel family
-// (-DPQP_TU=1..9, objects built in parallel by proxsuite_amd/_build.py); PQP_TU undefined or 0
-// compiles everything in one translation unit (the CPU emulator build of tests/emu does that).
+// The kernels of libproxqp_hip.so and their launchers.  Compiled once per kernel family (-DPQP_TU=k for every k of
+// KERNEL_TUS in proxsuite_amd/_build.py, the objects built in parallel); PQP_TU undefined or 0 compiles everything in
+// one translation unit (the CPU emulator build of tests/emu does that).
 //   1  pqp_solve_kernel<256, 4, 1>    no box constraints, dense Hessian (the C2 kernel): 128 VGPRs per
 //                                     lane, FOUR workgroups per CU -- launches that fill the device
 //   7  pqp_solve_kernel<256, 3, 1>    the same solve with 168 VGPRs per lane, three workgroups per CU:
 //                                     lower latency per QP, used when the launch leaves CUs idle anyway
-//   2  pqp_solve_kernel<256, 3, 0>
+//  15  pqp_solve_kernel<256, 2, 1>    ... 256 VGPRs, launches of at most two workgroups per CU
+//  13  pqp_solve_kernel<256, 1, 1>    ... the whole register file, launches of at most one workgroup per CU
+//   2  pqp_solve_kernel<256, 3, 0>    the general kernel: boxes, sparse Hessian types, PrimalLDLT
+//  14  pqp_solve_kernel<256, 1, 0>    ... launches of at most one workgroup per CU
 //   3  pqp_solve_kernel<512, 2, .>    256 VGPRs, one workgroup per CU
 //   8  pqp_solve_kernel<512, 4, .>    128 VGPRs, two workgroups per CU: launches of more workgroups than CUs
-//   4  pqp_solve_kernel<1024, ., .>
+//   4  pqp_solve_kernel<1024, 4, .>
 //   5  pqp_backward_kernel<.>
-//   6  pqp_setup_kernel<.>, pqp_order_kernel, the dispatchers
+//   6  pqp_setup_kernel<.>, pqp_order_kernel, pqp_pack_kernel and the host side of a solve launch:
+//      pqp_plan_solve (which kernel) and pqp_launch_solve (order, events, enqueue)
 #ifndef PQP_TU
 #define PQP_TU 0
 #endif
-//  12  pqp_solve_kernel<256, 3, 2>    the diagonal-structure solver alone (H diagonal / zero, no equality, every inequality
+//  12  pqp_solve_kernel<256, 2, 2>    the diagonal-structure solver alone (H diagonal / zero, no equality, every inequality
 //                                     row on one variable: BASELINE.json configs[4]): launches whose QPs ALL have it
-//   9  pqp_solve_hbm_kernel<1024, .>  shapes whose per-QP vectors exceed the CU's 160 KiB of LDS: the
+//  16  pqp_diag_kernel<E, 2>          that solver as one wavefront per QP (pqp_diag.hpp), E = 1, 2, 4 register slots per vector
+//   9  pqp_solve_hbm_kernel<1024, 4, .>  shapes whose per-QP vectors exceed the CU's 160 KiB of LDS: the
 //                                     SAME solver with its "LDS" pointers typed as global memory and
 //                                     carved out of a per-workgroup slice of an HBM scratch buffer (the
 //                                     workgroup barrier orders global accesses within a workgroup as it
@@ -80,97 +85,87 @@ pqp_solve_kernel(pqp::Batch batch, long first, const int* __restrict__ order)
   pqp::solve_body<NT, SPEC>(batch, first + slot, (pqp::lptr)smem);
 }
 
-template<int NT, int WPS, int SPEC>
-static int
-launch_solve(pqp_batch* h)
+// "name<A,...>": a kernel as the build's kernel-resource record (build/obj/*/kernel_resources.json) spells it, from
+// the template arguments that ARE instantiated (a variant library built with another PQP_WPS_* says so)
+template<int... A>
+static std::string
+kernel_label(const char* name)
 {
-  // (a kernel narrower than the handle's default width carves its own, smaller, LDS layout)
-  const size_t lds = (NT == h->nt) ? h->lds_solve : pqp::lds_bytes(h->dev.d, NT);
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&pqp_solve_kernel<NT, WPS, SPEC>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  HIP_TRY(hipEventRecord(h->ev0, h->stream));
-  const bool whole = h->range_first == 0 && h->range_count == h->dev.B;
-  const int* order = h->subset_order ? h->subset_order : ((h->lpt && h->order_valid && whole) ? h->d_order : nullptr);
-  hipLaunchKernelGGL((pqp_solve_kernel<NT, WPS, SPEC>), dim3((unsigned)h->range_count), dim3(NT), lds,
-                     h->stream, h->dev, h->range_first, order);
+  std::string s = std::string(name) + "<";
+  ((s += std::to_string(A) + ","), ...);
+  s.back() = '>';
+  return s;
+}
+
+// What every entry below does with its instantiation.  prepare: raise the kernel's dynamic-LDS limit where the launch
+// needs more than the default 64 KiB (pqp_launch_solve does this before it starts the clock).  Otherwise: enqueue it
+// over the QPs of the launch, workgroup i on QP range_first + (order ? order[i] : i), and note it as the handle's last
+// kernel.  `extra`: kernel arguments behind (batch, first, order).
+template<class K, class... Extra>
+static int
+enqueue(K* kernel, const std::string& label, pqp_batch* h, int threads, size_t lds, const int* order, bool prepare,
+        Extra... extra)
+{
+  if (prepare) {
+    if (lds > 64 * 1024)
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return PQP_OK;
+  }
+  hipLaunchKernelGGL((kernel), dim3((unsigned)h->range_count), dim3(threads), lds, h->stream, h->dev, h->range_first,
+                     order, extra...);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(h->ev1, h->stream));
+  h->last_kernel = label.c_str();
   return PQP_OK;
 }
 
-// SPEC = 1: no box constraints and a dense Hessian, both known at compile time
-int pqp_launch_solve_256_s1(pqp_batch* h);
-int pqp_launch_solve_256_s1_lat(pqp_batch* h);
-int pqp_launch_solve_256_s1_one(pqp_batch* h);
-int pqp_launch_solve_256_s0_one(pqp_batch* h);
-int pqp_launch_solve_256_s1_two(pqp_batch* h);
-int pqp_launch_solve_256_s0(pqp_batch* h);
-int pqp_launch_solve_256_s2(pqp_batch* h);
-int pqp_launch_solve_diag_wave(pqp_batch* h);
-int pqp_diag_wave_slots(int dim);
-int pqp_launch_dense_wave(pqp_batch* h);
-int pqp_launch_prologue(pqp_batch* h, long first, long count, hipStream_t stream);
-int pqp_launch_solve_512(pqp_batch* h, bool common);
-int pqp_launch_solve_512_dense(pqp_batch* h, bool common);
-int pqp_launch_solve_1024(pqp_batch* h, bool common);
-int pqp_launch_solve_hbm(pqp_batch* h, bool common);
+template<int NT, int WPS, int SPEC>
+static int
+enqueue_solve(pqp_batch* h, const LaunchPlan& p, const int* order, bool prepare)
+{
+  static const std::string label = kernel_label<NT, WPS, SPEC>("pqp_solve_kernel");
+  return enqueue(&pqp_solve_kernel<NT, WPS, SPEC>, label, h, NT, p.lds, order, prepare);
+}
+
+// One entry per translation unit, all of one signature: enqueue (or prepare) the instantiation the plan names.  An entry
+// is named after the PRODUCT's instantiation; a variant library may compile another register budget into it.
+using pqp_enqueue = int(pqp_batch* h, const LaunchPlan& p, const int* order, bool prepare);
+pqp_enqueue pqp_enqueue_256_4_1, pqp_enqueue_256_3_1, pqp_enqueue_256_2_1, pqp_enqueue_256_1_1, pqp_enqueue_256_3_0,
+  pqp_enqueue_256_1_0, pqp_enqueue_256_2_2, pqp_enqueue_diag_wave, pqp_enqueue_dense_wave, pqp_enqueue_prologue,
+  pqp_enqueue_512_2, pqp_enqueue_512_4, pqp_enqueue_1024, pqp_enqueue_hbm;
+#define PQP_SOLVE_ENTRY(name, NT, WPS, SPEC)                                                        \
+  int name(pqp_batch* h, const LaunchPlan& p, const int* order, bool prepare) { return enqueue_solve<NT, WPS, SPEC>(h, p, order, prepare); }
+#define PQP_SOLVE_ENTRY_1_0(name, NT, WPS, K_SPEC_1) /* both SPEC 1 (the plan's kernel is K_SPEC_1) and SPEC 0 */ \
+  int name(pqp_batch* h, const LaunchPlan& p, const int* order, bool prepare)                       \
+  {                                                                                                 \
+    return p.kernel == K_SPEC_1 ? enqueue_solve<NT, WPS, 1>(h, p, order, prepare) : enqueue_solve<NT, WPS, 0>(h, p, order, prepare); \
+  }
 
 #if PQP_TU_HAS(1)
-int
-pqp_launch_solve_256_s1(pqp_batch* h)
-{
-  return launch_solve<256, PQP_WPS_256_DENSE, 1>(h);
-}
+PQP_SOLVE_ENTRY(pqp_enqueue_256_4_1, 256, PQP_WPS_256_DENSE, 1)
 #endif
-
 #if PQP_TU_HAS(7)
-int
-pqp_launch_solve_256_s1_lat(pqp_batch* h)
-{
-  return launch_solve<256, PQP_WPS_256, 1>(h);
-}
+PQP_SOLVE_ENTRY(pqp_enqueue_256_3_1, 256, PQP_WPS_256, 1)
 #endif
 // One workgroup per CU: a launch of no more workgroups than the device has CUs (C1: 128 QPs, a single QP::solve())
 // leaves every QP a CU of its own, so the whole register file of a SIMD may go to its wavefront -- no spills at all
 // (100 spilled VGPRs at three per CU).  C1: 1.318 -> 1.245 ms (profiles/r04_ab_small_launch_budget.txt).
 #if PQP_TU_HAS(13)
-int
-pqp_launch_solve_256_s1_one(pqp_batch* h)
-{
-  return launch_solve<256, 1, 1>(h);
-}
+PQP_SOLVE_ENTRY(pqp_enqueue_256_1_1, 256, 1, 1)
 #endif
 #if PQP_TU_HAS(15)
-int
-pqp_launch_solve_256_s1_two(pqp_batch* h) // (up to two workgroups per CU: 256 VGPRs; 384 / 512 QPs of the C2 shape -3 %)
-{
-  return launch_solve<256, 2, 1>(h);
-}
+PQP_SOLVE_ENTRY(pqp_enqueue_256_2_1, 256, 2, 1) // (up to two workgroups per CU: 256 VGPRs; 384 / 512 QPs of the C2 shape -3 %)
 #endif
 #if PQP_TU_HAS(14)
-int
-pqp_launch_solve_256_s0_one(pqp_batch* h) // (the same for the general kernel: boxes, sparse Hessian types, PrimalLDLT)
-{
-  return launch_solve<256, 1, 0>(h);
-}
+PQP_SOLVE_ENTRY(pqp_enqueue_256_1_0, 256, 1, 0) // (one workgroup per CU for the general kernel: boxes, sparse Hessian types, PrimalLDLT)
 #endif
 #if PQP_TU_HAS(2)
-int
-pqp_launch_solve_256_s0(pqp_batch* h)
-{
-  return launch_solve<256, PQP_WPS_256, 0>(h);
-}
+PQP_SOLVE_ENTRY(pqp_enqueue_256_3_0, 256, PQP_WPS_256, 0)
 #endif
 #ifndef PQP_WPS_256_DIAG
 #define PQP_WPS_256_DIAG 2 // (two workgroups per CU at 256 VGPRs: 4.08 ms per 4096 C5 QPs against 4.29 ms with three at 168, profiles/r04_ab_diag_kernel.txt)
 #endif
 #if PQP_TU_HAS(12)
-int
-pqp_launch_solve_256_s2(pqp_batch* h)
-{
-  return launch_solve<256, PQP_WPS_256_DIAG, 2>(h);
-}
+PQP_SOLVE_ENTRY(pqp_enqueue_256_2_2, 256, PQP_WPS_256_DIAG, 2)
 #endif
 // One WAVEFRONT per QP, every per-QP vector in registers: the diagonal-structure solver of pqp_diag.hpp
 // (BASELINE.json configs[4]).  A workgroup is one wavefront; E = 4 register slots per vector serve dim <= 256, the
@@ -190,41 +185,30 @@ pqp_diag_kernel(pqp::Batch batch, long first, const int* __restrict__ order)
 
 template<int E>
 static int
-launch_diag_wave(pqp_batch* h)
+enqueue_diag(pqp_batch* h, const LaunchPlan& p, const int* order, bool prepare)
 {
-  HIP_TRY(hipEventRecord(h->ev0, h->stream));
-  const bool whole = h->range_first == 0 && h->range_count == h->dev.B;
-  const int* order = h->subset_order ? h->subset_order : ((h->lpt && h->order_valid && whole) ? h->d_order : nullptr);
-  hipLaunchKernelGGL((pqp_diag_kernel<E, PQP_WPS_DIAG_WAVE>), dim3((unsigned)h->range_count), dim3(64),
-                     pqp::diag_lds_bytes(E), h->stream, h->dev, h->range_first, order);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(h->ev1, h->stream));
-  return PQP_OK;
-}
-
-// register slots per vector by dimension: 1 (dim <= 64), 2 (<= 128), 4 (<= 256) -- a slot is a pass of every element-wise
-// loop over all 64 lanes, so a QP of dim 60 does a quarter of the vector instructions of one of dim 200
-int
-pqp_diag_wave_slots(int dim)
-{
-  return dim <= 64 ? 1 : (dim <= 128 ? 2 : 4);
+  static const std::string label = kernel_label<E, PQP_WPS_DIAG_WAVE>("pqp_diag_kernel");
+  return enqueue(&pqp_diag_kernel<E, PQP_WPS_DIAG_WAVE>, label, h, 64, p.lds, order, prepare);
 }
 
 int
-pqp_launch_solve_diag_wave(pqp_batch* h)
+pqp_enqueue_diag_wave(pqp_batch* h, const LaunchPlan& p, const int* order, bool prepare)
 {
-  switch (pqp_diag_wave_slots(h->dev.d.n)) {
-    case 1:
-      return launch_diag_wave<1>(h);
-    case 2:
-      return launch_diag_wave<2>(h);
+  switch (p.kernel) {
+    case PQP_K_DIAG_1:
+      return enqueue_diag<1>(h, p, order, prepare);
+    case PQP_K_DIAG_2:
+      return enqueue_diag<2>(h, p, order, prepare);
     default:
-      return launch_diag_wave<4>(h);
+      return enqueue_diag<4>(h, p, order, prepare);
   }
 }
 #endif
 // One WAVEFRONT per QP for DENSE QPs (pqp_dwave.hpp) behind the 256-thread factorisation prologue: two launches on the
-// handle's stream, one pair of events around both.
+// handle's stream, one pair of events around both and a third between them (pqp_launch_solve).
+// (Cutting the launch into 2 - 8 chunks on streams of their own, so that a chunk's prologue runs beside the iteration
+// kernel of the chunk before it, changes nothing: 7.67 - 7.93 ms against 7.69 ms per 2048 C2 QPs,
+// profiles/r06_ab_dwave.txt -- the pair is bound by the bytes it moves, not by the order it moves them in.)
 #if PQP_TU_HAS(18)
 template<int NT>
 __global__ __launch_bounds__(NT, 4) void
@@ -236,24 +220,12 @@ pqp_prologue_kernel(pqp::Batch batch, long first, const int* __restrict__ order)
   S.prologue();
 }
 
-// (first, count): the QPs of the launch this call covers (slots of the launch's order); stream: where it is enqueued
 int
-pqp_launch_prologue(pqp_batch* h, long first, long count, hipStream_t stream)
+pqp_enqueue_prologue(pqp_batch* h, const LaunchPlan&, const int* order, bool prepare)
 {
-  const size_t lds = (256 == h->nt) ? h->lds_solve : pqp::lds_bytes(h->dev.d, 256);
-  if (lds > 64 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&pqp_prologue_kernel<256>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const bool whole = h->range_first == 0 && h->range_count == h->dev.B;
-  const int* order = h->subset_order ? h->subset_order : ((h->lpt && h->order_valid && whole) ? h->d_order : nullptr);
-  if (order)
-    hipLaunchKernelGGL((pqp_prologue_kernel<256>), dim3((unsigned)count), dim3(256), lds, stream, h->dev, h->range_first,
-                       order + first);
-  else
-    hipLaunchKernelGGL((pqp_prologue_kernel<256>), dim3((unsigned)count), dim3(256), lds, stream, h->dev,
-                       h->range_first + first, order);
-  HIP_TRY(hipGetLastError());
-  return PQP_OK;
+  // (the plan's LDS is the iteration kernel's; the prologue is the 256-thread solver's and carves that layout)
+  static const std::string label = kernel_label<256>("pqp_prologue_kernel");
+  return enqueue(&pqp_prologue_kernel<256>, label, h, 256, h->lds_solve, order, prepare);
 }
 #endif
 #if PQP_TU_HAS(17)
@@ -269,47 +241,21 @@ pqp_dwave_kernel(pqp::Batch batch, long first, const int* __restrict__ order)
   pqp::dwave_solve_body(batch, first + slot, (pqp::lptr)smem);
 }
 
-// Two kernels per launch: the 256-thread factorisation prologue, then the one-wavefront iteration kernel.
-// (Cutting the launch into 2 - 8 chunks on streams of their own, so that a chunk's prologue runs beside the iteration
-// kernel of the chunk before it, changes nothing: 7.67 - 7.93 ms against 7.69 ms per 2048 C2 QPs,
-// profiles/r06_ab_dwave.txt -- the pair is bound by the bytes it moves, not by the order it moves them in.)
 int
-pqp_launch_dense_wave(pqp_batch* h)
+pqp_enqueue_dense_wave(pqp_batch* h, const LaunchPlan& p, const int* order, bool prepare)
 {
-  HIP_TRY(hipEventRecord(h->ev0, h->stream));
-  if (int rc = pqp_launch_prologue(h, 0, h->range_count, h->stream))
-    return rc;
-  HIP_TRY(hipEventRecord(h->ev_mid, h->stream));
-  h->prologue_timed = true;
-  const bool whole = h->range_first == 0 && h->range_count == h->dev.B;
-  const int* order = h->subset_order ? h->subset_order : ((h->lpt && h->order_valid && whole) ? h->d_order : nullptr);
-  hipLaunchKernelGGL((pqp_dwave_kernel<PQP_WPS_DENSE_WAVE>), dim3((unsigned)h->range_count), dim3(64), pqp::dwave_lds_bytes(),
-                     h->stream, h->dev, h->range_first, order);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(h->ev1, h->stream));
-  return PQP_OK;
+  static const std::string label = kernel_label<PQP_WPS_DENSE_WAVE>("pqp_dwave_kernel");
+  return enqueue(&pqp_dwave_kernel<PQP_WPS_DENSE_WAVE>, label, h, 64, p.lds, order, prepare);
 }
 #endif
 #if PQP_TU_HAS(3)
-int
-pqp_launch_solve_512(pqp_batch* h, bool common)
-{
-  return common ? launch_solve<512, PQP_WPS_512, 1>(h) : launch_solve<512, PQP_WPS_512, 0>(h);
-}
+PQP_SOLVE_ENTRY_1_0(pqp_enqueue_512_2, 512, PQP_WPS_512, PQP_K_512_2_1)
 #endif
 #if PQP_TU_HAS(8)
-int
-pqp_launch_solve_512_dense(pqp_batch* h, bool common)
-{
-  return common ? launch_solve<512, PQP_WPS_512_DENSE, 1>(h) : launch_solve<512, PQP_WPS_512_DENSE, 0>(h);
-}
+PQP_SOLVE_ENTRY_1_0(pqp_enqueue_512_4, 512, PQP_WPS_512_DENSE, PQP_K_512_4_1)
 #endif
 #if PQP_TU_HAS(4)
-int
-pqp_launch_solve_1024(pqp_batch* h, bool common)
-{
-  return common ? launch_solve<1024, PQP_WPS_1024, 1>(h) : launch_solve<1024, PQP_WPS_1024, 0>(h);
-}
+PQP_SOLVE_ENTRY_1_0(pqp_enqueue_1024, 1024, PQP_WPS_1024, PQP_K_1024_1)
 #endif
 
 #if PQP_TU == 9 || (PQP_TU == 0 && defined(PQP_EMULATED_MFMA))
@@ -323,22 +269,20 @@ pqp_solve_hbm_kernel(pqp::Batch batch, long first, const int* __restrict__ order
   pqp::solve_body<NT, SPEC>(batch, first + slot, (pqp::lptr)(scratch + (long)blockIdx.x * stride));
 }
 
-int
-pqp_launch_solve_hbm(pqp_batch* h, bool common)
+template<int SPEC>
+static int
+enqueue_hbm(pqp_batch* h, const LaunchPlan& p, const int* order, bool prepare)
 {
-  HIP_TRY(hipEventRecord(h->ev0, h->stream));
-  const bool whole = h->range_first == 0 && h->range_count == h->dev.B;
-  const int* order = h->subset_order ? h->subset_order : ((h->lpt && h->order_valid && whole) ? h->d_order : nullptr);
-  const long stride = (long)((h->lds_solve + 7) / 8);
-  if (common)
-    hipLaunchKernelGGL((pqp_solve_hbm_kernel<1024, PQP_WPS_1024, 1>), dim3((unsigned)h->range_count), dim3(1024), 0,
-                       h->stream, h->dev, h->range_first, order, h->vec_scratch, stride);
-  else
-    hipLaunchKernelGGL((pqp_solve_hbm_kernel<1024, PQP_WPS_1024, 0>), dim3((unsigned)h->range_count), dim3(1024), 0,
-                       h->stream, h->dev, h->range_first, order, h->vec_scratch, stride);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(h->ev1, h->stream));
-  return PQP_OK;
+  // (no dynamic LDS: workgroup i works on the i-th slice of p.lds bytes of the scratch buffer)
+  static const std::string label = kernel_label<1024, PQP_WPS_1024, SPEC>("pqp_solve_hbm_kernel");
+  return enqueue(&pqp_solve_hbm_kernel<1024, PQP_WPS_1024, SPEC>, label, h, 1024, 0, order, prepare, h->vec_scratch,
+                 (long)((p.lds + 7) / 8));
+}
+
+int
+pqp_enqueue_hbm(pqp_batch* h, const LaunchPlan& p, const int* order, bool prepare)
+{
+  return p.kernel == PQP_K_HBM_1 ? enqueue_hbm<1>(h, p, order, prepare) : enqueue_hbm<0>(h, p, order, prepare);
 }
 #endif
 
@@ -497,51 +441,34 @@ pqp_launch_pack(pqp_batch* h, long first, long count, double* out, hipStream_t s
   return PQP_OK;
 }
 
-// 0: the workgroup kernels; 1: every QP OF THE LAUNCH (its range or its subset; whole_batch: of the handle) has diagonal
-// structure (signature + the flags the set-up kernel left) and the launch goes to the one-wavefront kernel of pqp_diag.hpp;
-// 2: the same, forced to the 256-thread form of that solver by PQP_DIAG_KERNEL=workgroup (its A/B partner in the tests;
-// read per launch: they switch it between two solves).  (a general QP or a never-initialised slot elsewhere in
-// the handle no longer sends a launch of structured QPs to the 6.5 x slower kernel.)
-int
-pqp_diag_dispatch(const pqp_batch* h, bool whole_batch)
+// Every QP OF THE LAUNCH (its range or its subset) has diagonal structure: the signature, and the flag the set-up kernel
+// left for each of them (known once it has run: pqp_batch_flush).  (a general QP or a never-initialised slot
+// elsewhere in the handle no longer sends a launch of structured QPs to the 6.5 x slower kernel.)
+static bool
+diag_structure(const pqp_batch* h, long first, long count, const std::vector<int>* subset)
 {
   const pqp::Dims& dd = h->dev.d;
-  if (h->nt != 256 || h->vec_scratch || !pqp::diag_structure_signature(dd.hessian, dd.n_eq, dd.n_in, dd.box) || h->c_diag.empty())
-    return 0;
-  if (!whole_batch && h->subset_host) {
-    for (int q : *h->subset_host)
-      if (!h->c_diag[size_t(q)])
-        return 0;
-  } else {
-    const size_t lo = whole_batch ? 0 : size_t(h->range_first);
-    const size_t hi = whole_batch ? h->c_diag.size() : std::min(h->c_diag.size(), size_t(h->range_first + h->range_count));
-    for (size_t q = lo; q < hi; ++q)
-      if (!h->c_diag[q])
-        return 0;
-  }
-  const char* e = std::getenv("PQP_DIAG_KERNEL");
-  return (e && e[0] == 'w') || dd.n > 256 ? 2 : 1;
+  if (!pqp::diag_structure_signature(dd.hessian, dd.n_eq, dd.n_in, dd.box) || h->c_diag.empty())
+    return false;
+  if (subset)
+    return std::all_of(subset->begin(), subset->end(), [&](int q) { return h->c_diag[size_t(q)] != 0; });
+  const size_t hi = std::min(h->c_diag.size(), size_t(first + count));
+  return std::all_of(h->c_diag.begin() + std::min(size_t(first), hi), h->c_diag.begin() + hi, [](char c) { return c != 0; });
 }
 
-// 0: the workgroup kernels; 1: the one-wavefront dense kernel (pqp_dwave.hpp) behind the factorisation prologue.
+// A launch of `count` dense QPs goes to the one-wavefront kernel (pqp_dwave.hpp) behind the factorisation prologue.
 // PQP_DENSE_KERNEL=workgroup / wave forces either (the A/B partners of the tests; read per launch).  By default the
 // one-wavefront form takes the launches made of full resident rounds (see below).
-size_t
-pqp_dense_wave_lds_bytes()
+static bool
+dense_wave(const pqp_batch* h, long count)
 {
-  return pqp::dwave_lds_bytes();
-}
-
-int
-pqp_dense_wave_dispatch(const pqp_batch* h, long count)
-{
-  if (h->nt != 256 || h->vec_scratch || !pqp::dwave_signature(h->dev.d))
-    return 0;
+  if (!pqp::dwave_signature(h->dev.d))
+    return false;
   const char* e = std::getenv("PQP_DENSE_KERNEL");
   if (e && e[0] == 'w' && e[1] == 'o') // "workgroup"
-    return 0;
+    return false;
   if (e && e[0] == 'w' && e[1] == 'a') // "wave"
-    return 1;
+    return true;
   // Measured on C2-shaped batches, both kernels at 22 batch sizes (profiles/r06_ab_dwave.txt sections 5 and 17): the
   // one-wavefront kernel keeps 8 QPs per CU resident; it wins from 0.6 of a resident round upwards (1280 QPs on 256 CUs: +7 %;
   // 2048: +10 %) and in later rounds whenever the last one is empty or at least 0.4 full (3072: +6 %, 4096: +5 %); a thinner
@@ -550,51 +477,96 @@ pqp_dense_wave_dispatch(const pqp_batch* h, long count)
   // signature behave the same way (section 10).
   const long round = 8L * h->n_cu, rem = count % round;
   if (count < 64) // (whatever the device: a handful of QPs is a latency problem -- and the one-CU emulated device of the CPU tests
-    return 0;     //  dispatches small launches as a real one does)
+    return false; //  dispatches small launches as a real one does)
   if (count < round)
-    return (5 * count >= 3 * round) ? 1 : 0;
-  return (rem == 0 || 5 * rem >= 2 * round) ? 1 : 0;
+    return 5 * count >= 3 * round;
+  return rem == 0 || 5 * rem >= 2 * round;
 }
 
-int
-pqp_launch_solve(pqp_batch* h)
+LaunchPlan
+pqp_plan_solve(const pqp_batch* h, long first, long count, const std::vector<int>* subset)
 {
+  const pqp::Dims& dd = h->dev.d;
   // SPEC = 1: no box constraints, dense Hessian, PrimalDualLDLT engine -- all known at compile time
-  const bool common = h->dev.d.box == 0 && h->dev.d.hessian == PQP_HESSIAN_DENSE &&
-                      h->dev.d.backend != PQP_BACKEND_PRIMAL_LDLT;
-  h->prologue_timed = false;
-  {
-    // PQP_PRIMAL_REUSE=0: every solve factorises its primal block as if State::primal_valid did not exist (the A/B
-    // partner of the tests and of the measurements; read per launch, like PQP_DENSE_KERNEL)
-    const char* e = std::getenv("PQP_PRIMAL_REUSE");
-    h->dev.primal_reuse = (e && e[0] == '0') ? 0 : 1;
-  }
+  const bool common = dd.box == 0 && dd.hessian == PQP_HESSIAN_DENSE && dd.backend != PQP_BACKEND_PRIMAL_LDLT;
+  const long n_cu = h->n_cu;
+  const auto workgroup = [h](pqp_kernel k) { return LaunchPlan{ k, h->nt, h->lds_solve, false }; };
   if (h->vec_scratch) // per-QP vectors beyond the LDS of a CU: the solver runs on an HBM slice per workgroup
-    return pqp_launch_solve_hbm(h, common);
+    return workgroup(common ? PQP_K_HBM_1 : PQP_K_HBM_0);
   switch (h->nt) {
     case 256:
       if (!common) {
-        if (const int dg = pqp_diag_dispatch(h))
-          return dg == 1 ? pqp_launch_solve_diag_wave(h) : pqp_launch_solve_256_s2(h);
-        return (h->range_count <= (long)h->n_cu) ? pqp_launch_solve_256_s0_one(h) : pqp_launch_solve_256_s0(h);
+        if (diag_structure(h, first, count, subset)) {
+          // PQP_DIAG_KERNEL=workgroup forces the 256-thread form of that solver (its A/B partner in the tests; read per
+          // launch: they switch it between two solves)
+          const char* e = std::getenv("PQP_DIAG_KERNEL");
+          if ((e && e[0] == 'w') || dd.n > 256)
+            return workgroup(PQP_K_256_2_2);
+          // register slots per vector by dimension: 1 (dim <= 64), 2 (<= 128), 4 (<= 256) -- a slot is a pass of every
+          // element-wise loop over all 64 lanes, so a QP of dim 60 does a quarter of the vector instructions of one of dim 200
+          const int slots = dd.n <= 64 ? 1 : (dd.n <= 128 ? 2 : 4);
+          return LaunchPlan{ slots == 1 ? PQP_K_DIAG_1 : (slots == 2 ? PQP_K_DIAG_2 : PQP_K_DIAG_4), 64,
+                             pqp::diag_lds_bytes(slots), false };
+        }
+        return workgroup(count <= n_cu ? PQP_K_256_1_0 : PQP_K_256_3_0);
       }
-      if (pqp_dense_wave_dispatch(h, h->range_count))
-        return pqp_launch_dense_wave(h);
+      if (dense_wave(h, count))
+        return LaunchPlan{ PQP_K_DWAVE, 64, pqp::dwave_lds_bytes(), true };
       // more workgroups than three per CU can hold at once: the four-per-CU build; otherwise the
       // launch is latency-bound and the build with the larger register budget is faster per QP
-      if (h->range_count > 3L * h->n_cu && 4 * h->lds_solve <= 160 * 1024)
-        return pqp_launch_solve_256_s1(h);
-      if (h->range_count <= (long)h->n_cu)
-        return pqp_launch_solve_256_s1_one(h); // a CU per QP: the whole register file
-      if (h->range_count <= 2L * h->n_cu)
-        return pqp_launch_solve_256_s1_two(h);
-      return pqp_launch_solve_256_s1_lat(h);
+      if (count > 3 * n_cu && 4 * h->lds_solve <= 160 * 1024)
+        return workgroup(PQP_K_256_4_1);
+      if (count <= n_cu)
+        return workgroup(PQP_K_256_1_1); // a CU per QP: the whole register file
+      return workgroup(count <= 2 * n_cu ? PQP_K_256_2_1 : PQP_K_256_3_1);
     case 512:
       // (same rule as for 256 threads: the smaller register budget only when it buys a second resident workgroup)
-      return (h->range_count > (long)h->n_cu && 2 * h->lds_solve <= 160 * 1024) ? pqp_launch_solve_512_dense(h, common)
-                                                                               : pqp_launch_solve_512(h, common);
+      if (count > n_cu && 2 * h->lds_solve <= 160 * 1024)
+        return workgroup(common ? PQP_K_512_4_1 : PQP_K_512_4_0);
+      return workgroup(common ? PQP_K_512_2_1 : PQP_K_512_2_0);
     default:
-      return pqp_launch_solve_1024(h, common);
+      return workgroup(common ? PQP_K_1024_1 : PQP_K_1024_0);
   }
+}
+
+// the translation-unit entry of every pqp_kernel, in the order of the enum
+static pqp_enqueue* const ENTRY_OF[PQP_K_COUNT] = {
+  pqp_enqueue_256_4_1, pqp_enqueue_256_3_1, pqp_enqueue_256_2_1, pqp_enqueue_256_1_1, pqp_enqueue_256_3_0, pqp_enqueue_256_1_0,
+  pqp_enqueue_256_2_2, pqp_enqueue_diag_wave, pqp_enqueue_diag_wave, pqp_enqueue_diag_wave, pqp_enqueue_dense_wave,
+  pqp_enqueue_512_2, pqp_enqueue_512_2, pqp_enqueue_512_4, pqp_enqueue_512_4, pqp_enqueue_1024, pqp_enqueue_1024,
+  pqp_enqueue_hbm, pqp_enqueue_hbm
+};
+
+// One solve launch, as solve_impl left it in h->range_* / h->subset_*: planned once, then timed and enqueued here and
+// nowhere else -- ev0, the kernel(s), ev1, and ev_mid behind the prologue of a two-kernel launch.
+int
+pqp_launch_solve(pqp_batch* h)
+{
+  const LaunchPlan p = pqp_plan_solve(h, h->range_first, h->range_count, h->subset_host);
+  // PQP_PRIMAL_REUSE=0: every solve factorises its primal block as if State::primal_valid did not exist (the A/B
+  // partner of the tests and of the measurements; read per launch, like PQP_DENSE_KERNEL)
+  const char* reuse = std::getenv("PQP_PRIMAL_REUSE");
+  h->dev.primal_reuse = (reuse && reuse[0] == '0') ? 0 : 1;
+  // dispatch order of the QPs (workgroups are handed out in blockIdx order): the subset list, else the learned
+  // longest-first order of a whole-batch launch, else none
+  const bool whole = h->range_first == 0 && h->range_count == h->dev.B;
+  const int* order = h->subset_order ? h->subset_order : ((h->lpt && h->order_valid && whole) ? h->d_order : nullptr);
+  h->prologue_timed = false;
+  if (p.prologue)
+    if (int rc = pqp_enqueue_prologue(h, p, order, true))
+      return rc;
+  if (int rc = ENTRY_OF[p.kernel](h, p, order, true))
+    return rc;
+  HIP_TRY(hipEventRecord(h->ev0, h->stream));
+  if (p.prologue) {
+    if (int rc = pqp_enqueue_prologue(h, p, order, false))
+      return rc;
+    HIP_TRY(hipEventRecord(h->ev_mid, h->stream));
+    h->prologue_timed = true;
+  }
+  if (int rc = ENTRY_OF[p.kernel](h, p, order, false))
+    return rc;
+  HIP_TRY(hipEventRecord(h->ev1, h->stream));
+  return PQP_OK;
 }
 #endif

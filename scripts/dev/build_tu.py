@@ -27,13 +27,12 @@ for tu in tus:
     for k, v in B.parse_kernel_resources(r.stderr).items():
         print(B.kernel_label(k), {f: v[f] for f in ("VGPRs", "VGPRs_Spill", "SGPRs_Spill", "ScratchSize", "Occupancy") if f in v})
     print("compiled TU %d in %.0f s" % (tu, time.time() - t0))
-    repl[tu] = o
-capi = base / "capi.o"
+    repl["kernels_%d.o" % tu] = o
 if os.environ.get("CAPI"):
     capi = os.path.abspath(out) + ".capi.o"
     r = subprocess.run(["hipcc", *flags, "-c", os.path.join(src, "pqp_capi.hip"), "-o", capi], capture_output=True, text=True)
     if r.returncode:
         print(r.stderr[-6000:]); sys.exit(1)
-objs = [capi, base / "multi.o", base / "calib.o"] + [repl.get(k, base / ("kernels_%d.o" % k)) for k in B.KERNEL_TUS]
-subprocess.run(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, *map(str, objs)], check=True)
+    repl["capi.o"] = capi
+B.link_hip(out, base, repl)
 print("linked", out)

@@ -17,23 +17,32 @@ ROOT = HERE.parent.parent
 LIB = HERE / "libpqp_emu.so"
 
 
-def build_variant(tag, defines):
-    """A second emulator library with extra -D switches (A/B of a code path on the CPU: tests/test_emu_parity.py)."""
-    csrc = ROOT / "proxsuite_amd" / "csrc"
-    out = HERE / ("libpqp_emu_%s.so" % tag)
-    srcs = [csrc / "pqp_capi.hip", csrc / "pqp_multi.hip", csrc / "pqp_kernels.hip", csrc / "pqp_calib.hip", HERE / "hip_emu.cpp"]
-    deps = srcs + [csrc / "pqp_block.hpp", csrc / "pqp_solver.hpp", csrc / "pqp_host.hpp", csrc / "pqp_diag.hpp", csrc / "pqp_dwave.hpp", HERE / "hip_emu.hpp", Path(__file__)]
-    if out.exists() and all(d.stat().st_mtime <= out.stat().st_mtime for d in deps):
+CSRC = ROOT / "proxsuite_amd" / "csrc"
+
+
+def _compile(out, flags, force=False):
+    """the one g++ recipe: every product source in ONE translation-unit set against the emulator's hip_runtime.h; `out`
+    is rebuilt when a source, ANY header of csrc/, include/ or the emulator, or this file is newer"""
+    srcs = [CSRC / "pqp_capi.hip", CSRC / "pqp_multi.hip", CSRC / "pqp_kernels.hip", CSRC / "pqp_calib.hip", HERE / "hip_emu.cpp"]
+    deps = srcs + sorted(CSRC.glob("*.hpp")) + sorted((ROOT / "include").glob("*.h")) + \
+        [HERE / "hip_emu.hpp", HERE / "include" / "hip" / "hip_runtime.h", Path(__file__)]
+    if not force and out.exists() and all(d.stat().st_mtime <= out.stat().st_mtime for d in deps):
         return out
-    cmd = ["g++", "-std=gnu++17", "-fPIC", "-shared", "-O2", "-pthread", "-fno-strict-aliasing", "-DPQP_STATS",
-           *["-D" + d for d in defines], "-Wno-unknown-pragmas", "-Wno-attributes",
-           "-I", str(HERE / "include"), "-I", str(ROOT / "include"), "-I", str(csrc),
-           "-x", "c++", *map(str, srcs), "-o", str(out) + ".tmp%d" % os.getpid()]
+    tmp = str(out) + ".tmp%d" % os.getpid()
+    cmd = ["g++", "-std=gnu++17", "-fPIC", "-shared", *flags, "-pthread", "-fno-strict-aliasing", "-DPQP_STATS",
+           "-Wno-unknown-pragmas", "-Wno-attributes",
+           "-I", str(HERE / "include"), "-I", str(ROOT / "include"), "-I", str(CSRC),
+           "-x", "c++", *map(str, srcs), "-o", tmp]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
-        raise RuntimeError("emulator variant build failed:\n" + r.stdout + r.stderr)
-    os.replace(str(out) + ".tmp%d" % os.getpid(), out)  # (atomic: parallel test workers may build at the same time)
+        raise RuntimeError("emulator build of %s failed:\n" % out.name + r.stdout + r.stderr)
+    os.replace(tmp, out)  # (atomic: parallel test workers may build at the same time)
     return out
+
+
+def build_variant(tag, defines):
+    """A second emulator library with extra -D switches (A/B of a code path on the CPU: tests/test_emu_parity.py)."""
+    return _compile(HERE / ("libpqp_emu_%s.so" % tag), ["-O2", *["-D" + d for d in defines]])
 
 
 def build(force=False, debug=False):
@@ -41,23 +50,7 @@ def build(force=False, debug=False):
     # AddressSanitizer build, with LD_PRELOAD=libasan.so in front of python)
     if os.environ.get("PQP_EMU_LIBRARY"):
         return Path(os.environ["PQP_EMU_LIBRARY"])
-    csrc = ROOT / "proxsuite_amd" / "csrc"
-    srcs = [csrc / "pqp_capi.hip", csrc / "pqp_multi.hip", csrc / "pqp_kernels.hip", csrc / "pqp_calib.hip", HERE / "hip_emu.cpp"]
-    deps = srcs + [csrc / "pqp_block.hpp", csrc / "pqp_solver.hpp", csrc / "pqp_host.hpp", csrc / "pqp_diag.hpp", csrc / "pqp_dwave.hpp", HERE / "hip_emu.hpp",
-                   HERE / "include" / "hip" / "hip_runtime.h", ROOT / "include" / "proxqp_hip.h",
-                   ROOT / "include" / "pqp_types.h", Path(__file__)]
-    if not force and LIB.exists() and all(d.stat().st_mtime <= LIB.stat().st_mtime for d in deps):
-        return LIB
-    opt = ["-O0", "-g"] if debug else ["-O2"]
-    cmd = ["g++", "-std=gnu++17", "-fPIC", "-shared", *opt, "-pthread", "-fno-strict-aliasing", "-DPQP_STATS",
-           "-Wno-unknown-pragmas", "-Wno-attributes",
-           "-I", str(HERE / "include"), "-I", str(ROOT / "include"), "-I", str(csrc),
-           "-x", "c++", *map(str, srcs), "-o", str(LIB) + ".tmp%d" % os.getpid()]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("emulator build failed:\n" + r.stdout + r.stderr)
-    os.replace(str(LIB) + ".tmp%d" % os.getpid(), LIB)  # (atomic: parallel test workers may build at the same time)
-    return LIB
+    return _compile(LIB, ["-O0", "-g"] if debug else ["-O2"], force)
 
 
 if __name__ == "__main__":

@@ -319,15 +319,25 @@ def make_models(randqp, B, n, ne, ni, box, hessian, cond, seed0=0):
     return m, H, kw
 
 
+def kernel_threads(label):
+    """threads per workgroup of a solve kernel, from its label: the one-wavefront kernels run 64, the others say"""
+    if label.startswith(("pqp_diag_kernel<", "pqp_dwave_kernel<")):
+        return 64
+    assert label.startswith(("pqp_solve_kernel<", "pqp_solve_hbm_kernel<")), label
+    return int(label.split("<")[1].split(",")[0])
+
+
 def assert_kernel(b, threads=None, pair=None):
-    """what ran, from the launch itself: a case must not silently test the other kernel"""
-    t = b.launch_config()[0]
+    """what ran, from the launch itself (Batch.last_kernel: the label the launch left on the handle, not a forecast): a
+    case must not silently test the other kernel"""
+    k = b.last_kernel
+    assert k, "no solve has been launched"
     if pair is True:
-        assert t == 64 and b.last_prologue_ms > 0, ("the one-wavefront pair did not run", t, b.last_prologue_ms)
+        assert k.startswith("pqp_dwave_kernel<") and b.last_prologue_ms > 0, ("the one-wavefront pair did not run", k, b.last_prologue_ms)
     elif pair is False:
-        assert b.last_prologue_ms == 0, "the one-wavefront pair ran"
+        assert not k.startswith("pqp_dwave_kernel<") and b.last_prologue_ms == 0, ("the one-wavefront pair ran", k)
     if threads is not None:
-        assert t == threads, (t, threads)
+        assert kernel_threads(k) == threads, (k, threads)
 
 
 def solve_batch(lib, randqp, B, n, ne, ni, box=False, hessian=int(HessianType.Dense), cond=False, backend=0,

@@ -93,13 +93,15 @@ def oracle_solve(oracle, m, i, n, ne, ni, guess, **qpkw):
 
 
 def case_random_batch(lib, oracle, randqp, n, ne, ni, B, guess=InitialGuess.NO_INITIAL_GUESS, sparsity=0.15,
-                      compare=True, info_residuals=True):
-    """benchmark/timings-parallel.cpp:43-63 workload at arbitrary size."""
+                      compare=True, info_residuals=True, kernel=None):
+    """benchmark/timings-parallel.cpp:43-63 workload at arbitrary size.  `kernel`: the label the solve must leave in
+    Batch.last_kernel (the case is about that kernel)."""
     m = randqp.dense_strongly_convex_qp_batch(B, n, ne, ni, sparsity, 1e-2)
     b = N.Batch(B, n, ne, ni, lib=lib)
     settings_all(b, eps_abs=EPS, eps_rel=0, initial_guess=int(guess))
     b.init(-1, m.H, m.g, m.A, m.b, m.C, m.l, m.u)
     b.solve()
+    assert kernel is None or b.last_kernel == kernel, (b.last_kernel, kernel)
     x, y, z, se, si, info = b.results()
     for i in range(B):
         assert info[i].status == QPSolverOutput.PROXQP_SOLVED, (i, info[i].status)

@@ -128,7 +128,8 @@ def test_rows_beyond_the_workgroup(oracle, randqp):
         b = N.Batch(1, 30, 4, 600, lib=lib2)
         assert b.launch_config()[0] == 256
         b.close()
-        pc.case_random_batch(lib2, oracle, randqp, 30, 4, 600, B=2)
+        # (604 rows on 30 variables: the automatic choice takes PrimalLDLT, so the general 256-thread kernel -- nothing wider)
+        pc.case_random_batch(lib2, oracle, randqp, 30, 4, 600, B=2, kernel="pqp_solve_kernel<256,3,0>")
         pc.case_primal_ldlt(lib2, oracle, randqp, dim=280, B=1)
     finally:
         del os.environ["PQP_TEST_NT_MAX"]

@@ -354,7 +354,7 @@ def test_dense_wave_launch_forms(lib, randqp, monkeypatch):
 
     b = fresh()
     b.solve()
-    assert b.launch_config()[0] == 64 and b.last_prologue_ms > 0  # the pair ran
+    assert b.last_kernel.startswith("pqp_dwave_kernel<") and b.launch_config()[0] == 64 and b.last_prologue_ms > 0  # the pair ran
     ref = snap(b)
     assert all(s == 0 for s in ref[3][:, 0])
     b.close()

@@ -60,6 +60,13 @@ enum pqp_hessian_type
   PQP_HESSIAN_DIAGONAL = 2
 };
 
+/* EigenValueEstimateMethodOption, reference settings.hpp:49-53. */
+enum pqp_eig_method
+{
+  PQP_EIG_POWER_ITERATION = 0,
+  PQP_EIG_EXACT_METHOD = 1
+};
+
 /* MeritFunctionType, reference settings.hpp:36-40. */
 enum pqp_merit_function
 {

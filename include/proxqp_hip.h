@@ -76,6 +76,28 @@ int pqp_batch_update(pqp_batch* h, int64_t idx, const double* H, const double* g
                      const double* l_box, const double* u_box, int update_preconditioner,
                      double rho, double mu_eq, double mu_in, double manual_minimal_H_eigenvalue);
 
+/* pqp_batch_init / pqp_batch_update with ONE manual_minimal_H_eigenvalue PER ADDRESSED QP: a HOST array of B entries for
+ * idx == -1, of one entry otherwise.  A NaN entry, or a null pointer, means "absent", as the scalar's NaN does.  Everything
+ * else is the scalar entry's behaviour (an update that acts as a first init does not forward the value either). */
+int pqp_batch_init_eig(pqp_batch* h, int64_t idx, const double* H, const double* g, const double* A,
+                       const double* b, const double* C, const double* l, const double* u,
+                       const double* l_box, const double* u_box, int compute_preconditioner,
+                       double rho, double mu_eq, double mu_in, const double* manual_minimal_H_eigenvalue);
+int pqp_batch_update_eig(pqp_batch* h, int64_t idx, const double* H, const double* g, const double* A,
+                         const double* b, const double* C, const double* l, const double* u,
+                         const double* l_box, const double* u_box, int update_preconditioner,
+                         double rho, double mu_eq, double mu_in, const double* manual_minimal_H_eigenvalue);
+
+/* dense::estimate_minimal_eigen_value_of_symmetric_matrix (reference dense/helpers.hpp:24-166) on `count` symmetric
+ * matrices of order n at once, one workgroup per matrix: H is [count][n][n] row-major, out is [count]; both may be host
+ * or device memory (host input is staged to the device in one copy, device input is read in place).  `method` takes
+ * the values of EigenValueEstimateMethodOption (0 PowerIteration, 1 ExactMethod).  Synchronous.  1 <= n <= 8192
+ * (PQP_ERR_UNSUPPORTED above); count == 0 is a no-op.  PQP_ERR_INVALID_ARGUMENT "H is not symmetric." (with the index
+ * of the first offending matrix) under the reference's rule !H.isApprox(H^T, eps); `out` is then left unwritten. */
+int pqp_estimate_min_eigenvalues(int device, int64_t count, int64_t n, const double* H, int method,
+                                 double power_iteration_accuracy, int64_t nb_power_iteration, double* out,
+                                 void* stream);
+
 /* the warm-start half of QP::solve(x, y, z) (reference dense/wrapper.hpp:940-957,
  * helpers.hpp:715-763): stores the guess and switches initial_guess to WARM_START. */
 int pqp_batch_warm_start(pqp_batch* h, int64_t idx, const double* x, const double* y,
@@ -299,6 +321,16 @@ int pqp_multi_update(pqp_multi* m, int64_t idx, const double* H, const double* g
                      const double* C, const double* l, const double* u, const double* l_box, const double* u_box,
                      int update_preconditioner, double rho, double mu_eq, double mu_in,
                      double manual_minimal_H_eigenvalue);
+/* pqp_batch_init_eig / pqp_batch_update_eig over the shards: a HOST array with one entry per addressed QP (B for
+ * idx == -1), sliced along the shards; null = absent */
+int pqp_multi_init_eig(pqp_multi* m, int64_t idx, const double* H, const double* g, const double* A, const double* b,
+                       const double* C, const double* l, const double* u, const double* l_box, const double* u_box,
+                       int compute_preconditioner, double rho, double mu_eq, double mu_in,
+                       const double* manual_minimal_H_eigenvalue);
+int pqp_multi_update_eig(pqp_multi* m, int64_t idx, const double* H, const double* g, const double* A, const double* b,
+                         const double* C, const double* l, const double* u, const double* l_box, const double* u_box,
+                         int update_preconditioner, double rho, double mu_eq, double mu_in,
+                         const double* manual_minimal_H_eigenvalue);
 int pqp_multi_warm_start(pqp_multi* m, int64_t idx, const double* x, const double* y, const double* z);
 int pqp_multi_cleanup(pqp_multi* m, int64_t idx);
 int pqp_multi_flush(pqp_multi* m);

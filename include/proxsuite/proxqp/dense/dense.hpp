@@ -4,6 +4,7 @@
 #define PROXSUITE_AMD_PROXQP_DENSE_DENSE_HPP
 
 #include "proxsuite/proxqp/dense/compute_ECJ.hpp"
+#include "proxsuite/proxqp/dense/helpers.hpp"
 #include "proxsuite/proxqp/dense/wrapper.hpp"
 #include "proxsuite/proxqp/timings.hpp"
 

@@ -37,6 +37,13 @@ enum struct MeritFunctionType
   PDAL = PQP_MERIT_PDAL
 };
 
+// how estimate_minimal_eigen_value_of_symmetric_matrix works (reference settings.hpp:49-53)
+enum struct EigenValueEstimateMethodOption
+{
+  PowerIteration = PQP_EIG_POWER_ITERATION,
+  ExactMethod = PQP_EIG_EXACT_METHOD
+};
+
 template<typename T>
 struct Settings
 {

@@ -52,7 +52,11 @@ def build_randqp(force: bool = False) -> Path:
 # pqp_kernels.hip is compiled once per kernel family (see its header): every solve kernel is
 # ~350 KB of inlined code and takes about a minute of hipcc time, so the objects are built in
 # parallel and linked into one shared library.
-KERNEL_TUS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 14, 15, 16, 17, 18)
+KERNEL_TUS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 14, 15, 16, 17, 18, 19)
+# families outside the solver (19: the eigenvalue estimates of pqp_eig.hpp): built and linked like the others, their
+# resources frozen in a record of their own (tests/golden/eig_kernel_resources_expected.json) -- the solver's frozen record
+# names the solver's kernels and no others
+AUXILIARY_TUS = (19,)
 OBJ_DIR = ROOT / "build" / "obj"
 
 
@@ -168,7 +172,8 @@ def build_hip(force: bool = False, extra_flags=(), out: Path = None, tus=KERNEL_
     common = hip_headers() + [Path(__file__)]
     # (pqp_dwave.hpp is parsed by every kernel family; family 17 instantiates its kernel, and family 6 compiles the host
     # side of its dispatch -- pqp_plan_solve reads dwave_signature / dwave_lds_bytes: inline templates, no code elsewhere)
-    only = {"pqp_dwave.hpp": ("kernels_17.o", "kernels_6.o")}
+    # (pqp_eig.hpp: family 19 alone includes it; pqp_capi.hip reads its host half)
+    only = {"pqp_dwave.hpp": ("kernels_17.o", "kernels_6.o"), "pqp_eig.hpp": ("kernels_19.o", "capi.o")}
     def deps_of(o):
         return [h for h in common if h.name not in only or o.name in only[h.name]] + [CSRC / HOST_OBJECTS.get(o.name, "pqp_kernels.hip")]
     def compile_object(o):
@@ -191,13 +196,14 @@ def build_hip(force: bool = False, extra_flags=(), out: Path = None, tus=KERNEL_
     return lib
 
 
-def kernel_resources(tag: str = "default") -> dict:
-    """what the last build of `tag` recorded (see parse_kernel_resources)"""
+def kernel_resources(tag: str = "default", auxiliary: bool = False) -> dict:
+    """what the last build of `tag` recorded (see parse_kernel_resources) for the solver's kernel families, or
+    (`auxiliary`) for the families of AUXILIARY_TUS"""
     import json
     p = OBJ_DIR / tag / "kernel_resources.json"
     rec = json.loads(p.read_text()) if p.exists() else {}
     # (the record accumulates over builds: entries of translation units that no longer exist are dropped)
-    live = {"kernels_%d.o" % k for k in KERNEL_TUS}
+    live = {"kernels_%d.o" % k for k in KERNEL_TUS if (k in AUXILIARY_TUS) == auxiliary}
     return {k: v for k, v in rec.items() if v.get("object") in live}
 
 
@@ -283,6 +289,8 @@ def freeze_kernel_resources():
     out = {k: {f: v[f] for f in keep if f in v} for k, v in sorted(rec.items()) if k.startswith("pqp_")}
     p = ROOT / "tests" / "golden" / "kernel_resources_expected.json"
     p.write_text(json.dumps(out, indent=1, sort_keys=True))
+    aux = {k: {f: v[f] for f in keep if f in v} for k, v in sorted(kernel_resources(auxiliary=True).items()) if k.startswith("pqp_")}
+    (p.parent / "eig_kernel_resources_expected.json").write_text(json.dumps(aux, indent=1, sort_keys=True))
     return p
 
 

@@ -12,7 +12,7 @@ from pathlib import Path
 
 import numpy as np
 
-from ._ctypes_defs import pqp_info, pqp_settings
+from ._ctypes_defs import EigenValueEstimateMethodOption, pqp_info, pqp_settings
 
 PQP_STATS_COUNT = 33
 STAT_NAMES = ("cyc_total", "cyc_scale", "cyc_factor_h", "cyc_zg", "cyc_schur", "cyc_kkt_solve",
@@ -62,7 +62,8 @@ class NativeLib:
                "pqp_multi_cleanup", "pqp_multi_flush", "pqp_multi_solve", "pqp_multi_solve_range",
                "pqp_multi_solve_async", "pqp_multi_solve_range_async", "pqp_multi_wait", "pqp_multi_get_results",
                "pqp_multi_gather_device", "pqp_multi_get_trace", "pqp_multi_last_solve_ms", "pqp_box_calibrate",
-               "pqp_batch_host_results_fresh_range")
+               "pqp_batch_host_results_fresh_range", "pqp_batch_init_eig", "pqp_batch_update_eig", "pqp_multi_init_eig",
+               "pqp_multi_update_eig", "pqp_estimate_min_eigenvalues")
 
     def __init__(self, path, legacy=False):
         """legacy=True (A/B scripts only): an older build of the library that lacks the newer entries can still be
@@ -145,6 +146,9 @@ class NativeLib:
         L.pqp_multi_get_trace.argtypes = [vp, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         L.pqp_box_calibrate.argtypes = [C.c_int, _DP, C.c_int]
         L.pqp_batch_host_results_fresh_range.argtypes = [vp, C.c_int64, C.c_int64]
+        for name in ("pqp_batch_init_eig", "pqp_batch_update_eig", "pqp_multi_init_eig", "pqp_multi_update_eig"):
+            getattr(L, name).argtypes = [vp, C.c_int64] + [_DP] * 9 + [C.c_int] + [C.c_double] * 3 + [_DP]
+        L.pqp_estimate_min_eigenvalues.argtypes = [C.c_int, C.c_int64, C.c_int64, vp, C.c_int, C.c_double, C.c_int64, vp, vp]
         self.L = real
 
     def check(self, rc):
@@ -226,6 +230,52 @@ def _opt(v):
     return NAN if v is None else float(v)
 
 
+def _per_qp(v):
+    """manual_minimal_H_eigenvalue given as an ARRAY (one value per addressed QP) -> float64 host array; None for a scalar"""
+    if v is None or isinstance(v, (int, float)) or np.ndim(v) == 0:
+        return None
+    if hasattr(v, "detach"):
+        v = v.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+
+
+def estimate_min_eigenvalues(H, method=EigenValueEstimateMethodOption.ExactMethod, accuracy=1.0e-3, nb=1000, lib=None,
+                             device=0):
+    """pqp_estimate_min_eigenvalues (include/proxqp_hip.h): the reference's estimate_minimal_eigen_value_of_symmetric_matrix
+    on the B matrices of `H` ([B, n, n], numpy or torch, host or ROCm) in ONE launch, one workgroup per matrix.  Returns B
+    values: numpy for host input, a tensor on the same device for a ROCm tensor.  ValueError("H is not symmetric. ...")
+    names the first offending matrix."""
+    lib = lib if lib is not None else load()
+    method = int(EigenValueEstimateMethodOption(method))
+    if hasattr(H, "data_ptr"):
+        import torch
+        t = H.detach()
+        if t.dim() != 3 or t.shape[1] != t.shape[2]:
+            raise ValueError("wrong argument size: H has shape %s, expected [B, n, n]." % (tuple(t.shape),))
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            t = t.to(torch.float64).contiguous()
+        B, n = int(t.shape[0]), int(t.shape[1])
+        out = torch.empty(B, dtype=torch.float64, device=t.device)
+        stream = None
+        if t.is_cuda:
+            device = t.device.index if t.device.index is not None else torch.cuda.current_device()
+            stream = torch.cuda.current_stream(t.device).cuda_stream
+        if B:
+            lib.check(lib.L.pqp_estimate_min_eigenvalues(int(device), B, n, C.c_void_p(t.data_ptr()), method, float(accuracy),
+                                                         int(nb), C.c_void_p(out.data_ptr()),
+                                                         C.c_void_p(int(stream) if stream else None)))
+        return out
+    arr = np.ascontiguousarray(np.asarray(H, dtype=np.float64))
+    if arr.ndim != 3 or arr.shape[1] != arr.shape[2]:
+        raise ValueError("wrong argument size: H has shape %s, expected [B, n, n]." % (arr.shape,))
+    B, n = arr.shape[0], arr.shape[1]
+    out = np.empty(B)
+    if B:
+        lib.check(lib.L.pqp_estimate_min_eigenvalues(int(device), B, n, C.c_void_p(arr.ctypes.data), method, float(accuracy),
+                                                     int(nb), C.c_void_p(out.ctypes.data), None))
+    return out
+
+
 class Batch:
     """Thin object wrapper over a pqp_batch handle (one device, B QPs of identical sizes)."""
 
@@ -289,6 +339,16 @@ class Batch:
             k, p = _as_array(arr, sh[name], name)
             keep.append(k)
             ptrs.append(p)
+        per_qp = _per_qp(min_eig)
+        if per_qp is not None:
+            # one value per addressed QP: the _eig form of the same entry (pqp_batch_init -> pqp_batch_init_eig, ...)
+            want = self.B if idx < 0 else 1
+            if per_qp.size != want:
+                raise ValueError("wrong argument size: manual_minimal_H_eigenvalue has %d entries, expected %d" % (per_qp.size, want))
+            fn = getattr(self.lib.L, fn.__name__ + "_eig")
+            self.lib.check(fn(self._h, int(idx), *ptrs, int(bool(flag)), _opt(rho), _opt(mu_eq), _opt(mu_in),
+                              per_qp.ctypes.data_as(_DP)))
+            return
         self.lib.check(fn(self._h, int(idx), *ptrs, int(bool(flag)), _opt(rho), _opt(mu_eq), _opt(mu_in),
                           _opt(min_eig)))
 

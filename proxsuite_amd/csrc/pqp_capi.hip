@@ -15,6 +15,7 @@
 
 #include "pqp_host.hpp"
 #include "pqp_diag.hpp"
+#include "pqp_eig.hpp"
 
 namespace {
 
@@ -167,7 +168,7 @@ int
 enqueue_setup(pqp_batch* h, int64_t idx, bool update_call, const double* H, const double* g,
               const double* A, const double* b, const double* C, const double* l, const double* u,
               const double* l_box, const double* u_box, int precond_flag, double rho, double mu_eq,
-              double mu_in, double min_eig)
+              double mu_in, double min_eig, const double* min_eig_per_qp = nullptr)
 {
   if (int rc = check_idx(h, idx))
     return rc;
@@ -202,7 +203,8 @@ enqueue_setup(pqp_batch* h, int64_t idx, bool update_call, const double* H, cons
   for (int64_t q = lo; q < hi; ++q) {
     pqp_settings& st = h->settings[size_t(q)];
     bool is_init = !update_call || !h->is_initialized[size_t(q)];
-    double me = min_eig;
+    // (the _eig entries: a host array with one value per addressed QP; the scalar entries pass nullptr)
+    double me = min_eig_per_qp ? min_eig_per_qp[q - lo] : min_eig;
     if (update_call && is_init)
       me = std::numeric_limits<double>::quiet_NaN(); // wrapper.hpp:743-746 does not forward it
     host_settings_state_machine(st, is_init, precond_flag, rho, mu_eq, mu_in, me);
@@ -515,6 +517,118 @@ pqp_batch_update(pqp_batch* h, int64_t idx, const double* H, const double* g, co
 {
   return enqueue_setup(h, idx, true, H, g, A, b, C, l, u, l_box, u_box, update_preconditioner ? 1 : 0,
                        rho, mu_eq, mu_in, manual_minimal_H_eigenvalue);
+}
+
+int
+pqp_batch_init_eig(pqp_batch* h, int64_t idx, const double* H, const double* g, const double* A,
+                   const double* b, const double* C, const double* l, const double* u,
+                   const double* l_box, const double* u_box, int compute_preconditioner, double rho,
+                   double mu_eq, double mu_in, const double* manual_minimal_H_eigenvalue)
+{
+  if (h && h->dev.d.box == 0 && (l_box || u_box))
+    return fail(PQP_ERR_INVALID_ARGUMENT,
+                "wrong model setup: the QP object is designed without box constraints, but is "
+                "initialized with lower or upper box inequalities."); // wrapper.hpp:542-546
+  return enqueue_setup(h, idx, false, H, g, A, b, C, l, u, l_box, u_box, compute_preconditioner ? 1 : 0,
+                       rho, mu_eq, mu_in, std::numeric_limits<double>::quiet_NaN(), manual_minimal_H_eigenvalue);
+}
+
+int
+pqp_batch_update_eig(pqp_batch* h, int64_t idx, const double* H, const double* g, const double* A,
+                     const double* b, const double* C, const double* l, const double* u,
+                     const double* l_box, const double* u_box, int update_preconditioner, double rho,
+                     double mu_eq, double mu_in, const double* manual_minimal_H_eigenvalue)
+{
+  return enqueue_setup(h, idx, true, H, g, A, b, C, l, u, l_box, u_box, update_preconditioner ? 1 : 0,
+                       rho, mu_eq, mu_in, std::numeric_limits<double>::quiet_NaN(), manual_minimal_H_eigenvalue);
+}
+
+// dense::estimate_minimal_eigen_value_of_symmetric_matrix on `count` matrices in one launch (pqp_eig.hpp)
+int
+pqp_estimate_min_eigenvalues(int device, int64_t count, int64_t n, const double* H, int method,
+                             double power_iteration_accuracy, int64_t nb_power_iteration, double* out, void* stream)
+{
+  if (count < 0)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "negative number of matrices");
+  if (count == 0)
+    return PQP_OK;
+  if (!H || !out)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "null argument");
+  if (method != PQP_EIG_POWER_ITERATION && method != PQP_EIG_EXACT_METHOD)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "unknown eigenvalue estimate method");
+  if (n < 1) // (the reference's Eigen calls have nothing to work on)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "the order of H should be strictly positive.");
+  if (n > PQP_MAX_ROWS)
+    return fail(PQP_ERR_UNSUPPORTED, "order of H > " + std::to_string(PQP_MAX_ROWS) + " is not supported by this build");
+  if (count > 0x7fffffffll)
+    return fail(PQP_ERR_UNSUPPORTED, "more than 2^31 - 1 matrices in one call");
+  int ndev = pqp_device_count();
+  if (ndev <= 0)
+    return fail(PQP_ERR_NO_DEVICE, "no HIP device: libproxqp_hip has no CPU fallback");
+  if (device < 0 || device >= ndev)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "device ordinal out of range");
+  PQP_ON_DEVICE(device);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // everything the call allocates, freed on every way out
+  struct Scratch
+  {
+    std::vector<void*> p;
+    ~Scratch()
+    {
+      for (void* q : p)
+        (void)hipFree(q);
+    }
+    int get(void** out, size_t bytes)
+    {
+      HIP_TRY(hipMalloc(out, bytes));
+      p.push_back(*out);
+      return PQP_OK;
+    }
+  } scratch;
+  const size_t nn = size_t(n) * size_t(n), B = size_t(count);
+  pqp::EigArgs a{};
+  a.n = int(n);
+  a.method = method;
+  a.accuracy = power_iteration_accuracy;
+  a.nb = long(nb_power_iteration);
+  a.H = H;
+  if (!pqp_device_readable(H)) { // host input: staged to the device in one copy
+    void* d = nullptr;
+    if (int rc = scratch.get(&d, B * nn * sizeof(double)))
+      return rc;
+    HIP_TRY(hipMemcpyAsync(d, H, B * nn * sizeof(double), hipMemcpyHostToDevice, st));
+    a.H = static_cast<const double*>(d);
+  }
+  // per matrix: the estimate, ||H - H^T||_F and ||H||_F
+  void* d_res = nullptr;
+  if (int rc = scratch.get(&d_res, B * 3 * sizeof(double)))
+    return rc;
+  a.res = static_cast<double*>(d_res);
+  // PQP_EIG_RESIDENT=0 / 1 forces the streamed / the LDS-resident form where both exist (the A/B partners of
+  // scripts/eig_bench.py and of the tests; read per call)
+  a.resident = pqp::eig_resident(a.n) ? 1 : 0;
+  if (const char* e = std::getenv("PQP_EIG_RESIDENT"))
+    a.resident = (e[0] == '1' && pqp::eig_lds_bytes(a.n, true) <= 160 * 1024) ? 1 : (e[0] == '0' ? 0 : a.resident);
+  if (method == PQP_EIG_EXACT_METHOD && !a.resident) { // the working copy of the tridiagonalisation: a slice of HBM per matrix
+    void* w = nullptr;
+    if (int rc = scratch.get(&w, B * nn * sizeof(double)))
+      return rc;
+    a.work = static_cast<double*>(w);
+  }
+  if (int rc = pqp_launch_eig(a, long(count), st))
+    return rc;
+  std::vector<double> res(B * 3);
+  HIP_TRY(hipMemcpyAsync(res.data(), d_res, B * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  // helpers.hpp:131-134: !H.isApprox(H^T, eps)  <=>  ||H - H^T||_F > eps min(||H||_F, ||H^T||_F)  (a zero matrix passes)
+  for (size_t q = 0; q < B; ++q)
+    if (!(res[3 * q + 1] <= std::numeric_limits<double>::epsilon() * res[3 * q + 2]))
+      return fail(PQP_ERR_INVALID_ARGUMENT, "H is not symmetric. (matrix " + std::to_string(q) + " of the batch)");
+  std::vector<double> vals(B);
+  for (size_t q = 0; q < B; ++q)
+    vals[q] = res[3 * q];
+  HIP_TRY(hipMemcpy(out, vals.data(), B * sizeof(double), hipMemcpyDefault));
+  return PQP_OK;
 }
 
 int

@@ -51,8 +51,14 @@
 //  17  pqp_dwave_kernel<WPS>          the DENSE solver as one wavefront per QP (pqp_dwave.hpp): dense Hessian, no box, n, n_eq,
 //                                     n_in <= 128 -- the iteration of a solve; launches that fill the device
 //  18  pqp_prologue_kernel<256>       the factorisation prologue of those solves (Solver::prologue), 256 threads per QP
+//  19  pqp_eig_kernel<256, M>         batched minimal-eigenvalue estimates (pqp_eig.hpp), one workgroup per matrix: M = 0 the
+//                                     reference's power iteration, 1 Householder tridiagonalisation + Sturm multisection
 #include "pqp_host.hpp"
 #include "pqp_dwave.hpp"
+#if PQP_TU == 0 || PQP_TU == 19
+#define PQP_EIG_DEVICE 1
+#include "pqp_eig.hpp"
+#endif
 
 #define PQP_TU_HAS(k) (PQP_TU == 0 || PQP_TU == (k))
 
@@ -283,6 +289,36 @@ int
 pqp_enqueue_hbm(pqp_batch* h, const LaunchPlan& p, const int* order, bool prepare)
 {
   return p.kernel == PQP_K_HBM_1 ? enqueue_hbm<1>(h, p, order, prepare) : enqueue_hbm<0>(h, p, order, prepare);
+}
+#endif
+
+#if PQP_TU_HAS(19)
+template<int NT, int METHOD>
+__global__ __launch_bounds__(NT) void
+pqp_eig_kernel(pqp::EigArgs a)
+{
+  HIP_DYNAMIC_SHARED(double, smem)
+  pqp::eig_body<NT, METHOD>(a, (long)blockIdx.x, (pqp::lptr)smem);
+}
+
+template<int METHOD>
+static int
+launch_eig(const pqp::EigArgs& a, long count, hipStream_t stream)
+{
+  const size_t lds = pqp::eig_lds_bytes(a.n, a.resident != 0);
+  if (lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&pqp_eig_kernel<pqp::EIG_NT, METHOD>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((pqp_eig_kernel<pqp::EIG_NT, METHOD>), dim3((unsigned)count), dim3(pqp::EIG_NT), lds, stream, a);
+  HIP_TRY(hipGetLastError());
+  return PQP_OK;
+}
+
+int
+pqp_launch_eig(const pqp::EigArgs& a, long count, hipStream_t stream)
+{
+  return a.method == PQP_EIG_POWER_ITERATION ? launch_eig<PQP_EIG_POWER_ITERATION>(a, count, stream)
+                                             : launch_eig<PQP_EIG_EXACT_METHOD>(a, count, stream);
 }
 #endif
 

@@ -57,9 +57,6 @@ off(double* p, int64_t first, size_t per_qp)
   return p ? p + size_t(first) * per_qp : nullptr;
 }
 
-typedef int (*setup_fn)(pqp_batch*, int64_t, const double*, const double*, const double*, const double*, const double*,
-                        const double*, const double*, const double*, const double*, int, double, double, double, double);
-
 // Runs `work(s)` for every shard that holds QPs, all of them at once: one host thread per shard (the caller's takes the
 // first).  A set-up is a blocking copy of the shard's slice of the model from pageable host memory plus, at flush time,
 // the set-up kernel and a read-back of its flags -- walked shard after shard (rounds 3-4) the G devices of a node worked
@@ -100,10 +97,24 @@ for_shards(pqp_multi* m, F&& work)
   return PQP_OK;
 }
 
+// the manual_minimal_H_eigenvalue of shard-local QP range [f, ...): the one scalar, or the slice of the per-QP array
+inline double
+eig_from(double v, int64_t)
+{
+  return v;
+}
+inline const double*
+eig_from(const double* p, int64_t f)
+{
+  return off(p, f, 1);
+}
+
+// Fn / Eig: pqp_batch_init / pqp_batch_update with a scalar, or their _eig forms with a host array (one entry per addressed QP)
+template<class Fn, class Eig>
 int
-multi_setup(pqp_multi* m, setup_fn fn, int64_t idx, const double* H, const double* g, const double* A, const double* b,
+multi_setup(pqp_multi* m, Fn fn, int64_t idx, const double* H, const double* g, const double* A, const double* b,
             const double* C, const double* l, const double* u, const double* l_box, const double* u_box, int flag,
-            double rho, double mu_eq, double mu_in, double min_eig)
+            double rho, double mu_eq, double mu_in, Eig min_eig)
 {
   if (int rc = check_multi_idx(m, idx))
     return rc;
@@ -118,7 +129,7 @@ multi_setup(pqp_multi* m, setup_fn fn, int64_t idx, const double* H, const doubl
   return for_shards(m, [&](size_t s) {
     const int64_t f = m->first[s];
     return fn(m->shard[s], -1, off(H, f, n * n), off(g, f, n), off(A, f, ne * n), off(b, f, ne), off(C, f, ni * n),
-              off(l, f, ni), off(u, f, ni), off(l_box, f, n), off(u_box, f, n), flag, rho, mu_eq, mu_in, min_eig);
+              off(l, f, ni), off(u, f, ni), off(l_box, f, n), off(u_box, f, n), flag, rho, mu_eq, mu_in, eig_from(min_eig, f));
   });
 }
 
@@ -264,6 +275,26 @@ pqp_multi_update(pqp_multi* m, int64_t idx, const double* H, const double* g, co
                  int update_preconditioner, double rho, double mu_eq, double mu_in, double manual_minimal_H_eigenvalue)
 {
   return multi_setup(m, pqp_batch_update, idx, H, g, A, b, C, l, u, l_box, u_box, update_preconditioner, rho, mu_eq, mu_in,
+                     manual_minimal_H_eigenvalue);
+}
+
+int
+pqp_multi_init_eig(pqp_multi* m, int64_t idx, const double* H, const double* g, const double* A, const double* b,
+                   const double* C, const double* l, const double* u, const double* l_box, const double* u_box,
+                   int compute_preconditioner, double rho, double mu_eq, double mu_in,
+                   const double* manual_minimal_H_eigenvalue)
+{
+  return multi_setup(m, pqp_batch_init_eig, idx, H, g, A, b, C, l, u, l_box, u_box, compute_preconditioner, rho, mu_eq, mu_in,
+                     manual_minimal_H_eigenvalue);
+}
+
+int
+pqp_multi_update_eig(pqp_multi* m, int64_t idx, const double* H, const double* g, const double* A, const double* b,
+                     const double* C, const double* l, const double* u, const double* l_box, const double* u_box,
+                     int update_preconditioner, double rho, double mu_eq, double mu_in,
+                     const double* manual_minimal_H_eigenvalue)
+{
+  return multi_setup(m, pqp_batch_update_eig, idx, H, g, A, b, C, l, u, l_box, u_box, update_preconditioner, rho, mu_eq, mu_in,
                      manual_minimal_H_eigenvalue);
 }
 

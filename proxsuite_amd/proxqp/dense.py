@@ -496,7 +496,17 @@ def estimate_minimal_eigen_value_of_symmetric_matrix(H, estimate_method_option=E
     """Host-side helper for non-convex QPs, as in the reference (dense/helpers.hpp:24-165, python
     expose-helpers.hpp:22-46): the value goes to `init(..., manual_minimal_H_eigenvalue=...)`.
     ExactMethod = smallest eigenvalue (Householder + Sturm bisection in libpqp_randqp.so);
-    PowerIteration = the reference's two power iterations, restated."""
+    PowerIteration = the reference's two power iterations, restated.
+    A 3-D `H` ([B, n, n]) is a batch: both methods then run on the device, one workgroup per matrix, and B values come
+    back (numpy for host input, a tensor on the same device for a ROCm tensor)."""
+    if (H.dim() if hasattr(H, "data_ptr") else np.ndim(H)) == 3:
+        # a batch [B, n, n] (numpy or torch, host or ROCm): one device launch, B values (pqp_estimate_min_eigenvalues)
+        try:
+            return _native.estimate_min_eigenvalues(H, estimate_method_option, power_iteration_accuracy, nb_power_iteration)
+        except ValueError as e:
+            if str(e).startswith("H is not symmetric."):
+                raise ValueError("H is not symmetric.") from e  # (the cause names the first offending matrix)
+            raise
     H = np.ascontiguousarray(np.asarray(H, dtype=np.float64))
     if H.ndim != 2 or H.shape[0] != H.shape[1]:
         raise ValueError("wrong argument size: H has a number of rows different of the number of columns.")

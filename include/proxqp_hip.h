@@ -191,6 +191,23 @@ int pqp_batch_backward_range(pqp_batch* h, int64_t first, int64_t count, const d
  * `count` QPs idx[0..count) in ONE launch; row i of loss_derivatives ([count][dim + n_eq + n_in]) belongs to QP idx[i]. */
 int pqp_batch_backward_subset(pqp_batch* h, const int64_t* idx, int64_t count, const double* loss_derivatives,
                               double eps, double rho_backward, double mu_backward);
+/* The same backward pass for n_rhs loss derivatives per QP in one launch: the active set and the factorisation at
+ * (rho_backward, mu_backward) depend on the solved QP only and are done once per QP, the refined KKT solve once per row,
+ * the rows one after the other -- a row's arithmetic is that of a single pqp_batch_backward_range call.
+ * `loss_derivatives` and `out` are [count][n_rhs][dim + n_eq + n_in], host or device memory (host arrays are staged
+ * through buffers of the handle, device memory is used in place).  Row k of `out` is the unscaled solution
+ * V = (V_x, V_y, V_z) the jacobians are formed from: dL_dg = V_x, dL_db = -V_y, dL_du = -V_z where the constraint is
+ * active from above (else 0), dL_dl = -V_z where it is active from below, dL_dH = (V_x x^T + x V_x^T) / 2,
+ * dL_dA = V_y x^T + y V_x^T, dL_dC = V_z x^T + z V_x^T.  `active` (may be NULL) is [count][n_in]: bit 0 = active from
+ * above, bit 1 = from below.  The buffers of pqp_batch_get_backward are not filled.  Synchronous.  Errors as
+ * pqp_batch_backward_range; n_rhs < 0 or a size that overflows: PQP_ERR_INVALID_ARGUMENT; n_rhs == 0 or count == 0:
+ * PQP_OK, nothing is touched.  The QPs' state afterwards is that after pqp_batch_backward_range. */
+int pqp_batch_backward_multi(pqp_batch* h, int64_t first, int64_t count, int64_t n_rhs, const double* loss_derivatives,
+                             double eps, double rho_backward, double mu_backward, double* out, int32_t* active);
+/* ... on the `count` QPs idx[0..count): slot i of loss_derivatives / out / active belongs to QP idx[i] */
+int pqp_batch_backward_multi_subset(pqp_batch* h, const int64_t* idx, int64_t count, int64_t n_rhs,
+                                    const double* loss_derivatives, double eps, double rho_backward, double mu_backward,
+                                    double* out, int32_t* active);
 /* Model::backward_data (reference dense/backward_data.hpp:27-133) of QP idx (-1: the whole
  * batch, arrays [B][...]); row-major; any pointer may be NULL. */
 int pqp_batch_get_backward(pqp_batch* h, int64_t idx, double* dL_dH, double* dL_dg, double* dL_dA,

@@ -2,9 +2,13 @@
 // loss wrt (H, g, A, b, C, u, l) of a SOLVED QP given dL/d(x, y, z), written to
 // qp.model.backward_data.  Same signature and defaults as the reference
 // (include/proxsuite/proxqp/dense/compute_ECJ.hpp:29-132); the work is one launch of
-// pqp_backward_kernel through pqp_batch_backward_range (include/proxqp_hip.h).
+// pqp_backward_kernel through pqp_batch_backward_range (include/proxqp_hip.h).  compute_backward_multi /
+// solution_jacobians: K loss derivatives of one QP in one launch (pqp_batch_backward_multi).
 #ifndef PROXSUITE_AMD_PROXQP_DENSE_COMPUTE_ECJ_HPP
 #define PROXSUITE_AMD_PROXQP_DENSE_COMPUTE_ECJ_HPP
+
+#include <cstdint>
+#include <vector>
 
 #include "proxsuite/proxqp/dense/wrapper.hpp"
 
@@ -44,6 +48,71 @@ compute_backward(QP<T>& solved_qp, VecRef<T> loss_derivative, T eps = 1.E-4, T r
   detail::check(pqp_batch_backward_range(solved_qp.pool()->h, solved_qp.slot(), 1, p, eps, rho_new, mu_new));
   detail::pull_backward(solved_qp);
   solved_qp.pull(); // results.info carries the backward proximal parameters, as in the reference
+}
+
+// compute_backward for K loss derivatives (the rows of `loss_derivatives`, K x (dim + n_eq + n_in)) of one solved QP in
+// ONE launch (pqp_batch_backward_multi): the factorisation at (rho_new, mu_new) is done once, the refined KKT solve per
+// row.  Returns the K x (dim + n_eq + n_in) matrix of rows (V_x, V_y, V_z): dL_dg = V_x, dL_db = -V_y, dL_du / dL_dl =
+// -V_z where the constraint is active from above / below (`active`, optional: n_in flags, bit 0 above, bit 1 below).
+// qp.model.backward_data is left alone.
+template<typename T>
+Mat<T>
+compute_backward_multi(QP<T>& solved_qp,
+                       MatRef<T> loss_derivatives,
+                       T eps = 1.E-4,
+                       T rho_new = 1.E-6,
+                       T mu_new = 1.E-6,
+                       std::vector<std::int32_t>* active = nullptr)
+{
+  const isize ntot = solved_qp.model.dim + solved_qp.model.n_eq + solved_qp.model.n_in;
+  if (loss_derivatives.cols() != ntot)
+    detail::bad_size("a loss derivative has dim + n_eq + n_in entries.", loss_derivatives.cols(), ntot);
+  const isize K = loss_derivatives.rows();
+  Mat<T> ld(K, ntot), out(K, ntot);
+  for (isize k = 0; k < K; ++k)
+    for (isize i = 0; i < ntot; ++i)
+      ld(k, i) = loss_derivatives(k, i);
+  std::vector<std::int32_t> flags(usize(solved_qp.model.n_in), 0);
+  detail::PoolLock lock(solved_qp.pool()->mtx);
+  solved_qp.push_settings();
+  detail::check(pqp_batch_backward_multi(solved_qp.pool()->h, solved_qp.slot(), 1, K, ld.data(), eps, rho_new, mu_new,
+                                         out.data(), flags.data()));
+  solved_qp.pull(); // results.info carries the backward proximal parameters, as after compute_backward
+  if (active)
+    *active = flags;
+  return out;
+}
+
+// The jacobians of the solution x of a solved QP wrt its vectors, from ONE call with the K = dim loss derivatives
+// [I | 0]: row i holds compute_backward's dL_dg, dL_db, dL_du, dL_dl for the loss x_i.
+template<typename T>
+struct SolutionJacobians
+{
+  Mat<T> dx_dg, dx_db, dx_du, dx_dl; // dim x dim, dim x n_eq, dim x n_in, dim x n_in
+};
+
+template<typename T>
+SolutionJacobians<T>
+solution_jacobians(QP<T>& solved_qp, T eps = 1.E-4, T rho_new = 1.E-6, T mu_new = 1.E-6)
+{
+  const isize n = solved_qp.model.dim, ne = solved_qp.model.n_eq, ni = solved_qp.model.n_in;
+  Mat<T> ld(n, n + ne + ni);
+  for (isize i = 0; i < n; ++i)
+    ld(i, i) = T(1);
+  std::vector<std::int32_t> active;
+  const Mat<T> V = compute_backward_multi(solved_qp, MatRef<T>(ld), eps, rho_new, mu_new, &active);
+  SolutionJacobians<T> J{ Mat<T>(n, n), Mat<T>(n, ne), Mat<T>(n, ni), Mat<T>(n, ni) };
+  for (isize i = 0; i < n; ++i) {
+    for (isize k = 0; k < n; ++k)
+      J.dx_dg(i, k) = V(i, k);
+    for (isize k = 0; k < ne; ++k)
+      J.dx_db(i, k) = -V(i, n + k);
+    for (isize k = 0; k < ni; ++k) {
+      J.dx_du(i, k) = (active[usize(k)] & 1) ? -V(i, n + ne + k) : T(0);
+      J.dx_dl(i, k) = (active[usize(k)] & 2) ? -V(i, n + ne + k) : T(0);
+    }
+  }
+  return J;
 }
 
 } // namespace dense

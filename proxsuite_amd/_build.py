@@ -52,11 +52,15 @@ def build_randqp(force: bool = False) -> Path:
 # pqp_kernels.hip is compiled once per kernel family (see its header): every solve kernel is
 # ~350 KB of inlined code and takes about a minute of hipcc time, so the objects are built in
 # parallel and linked into one shared library.
-KERNEL_TUS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 14, 15, 16, 17, 18, 19)
+KERNEL_TUS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21)
 # families outside the solver (19: the eigenvalue estimates of pqp_eig.hpp): built and linked like the others, their
 # resources frozen in a record of their own (tests/golden/eig_kernel_resources_expected.json) -- the solver's frozen record
 # names the solver's kernels and no others
 AUXILIARY_TUS = (19,)
+# ... and further groups of that kind, each with a frozen record of its own and selected by name
+# (kernel_resources(auxiliary="backward_multi")): 20 / 21, the backward pass for K loss derivatives per QP, in LDS and on
+# an HBM slice (tests/golden/backward_multi_kernel_resources_expected.json)
+NAMED_TUS = {"backward_multi": (20, 21)}
 OBJ_DIR = ROOT / "build" / "obj"
 
 
@@ -196,14 +200,18 @@ def build_hip(force: bool = False, extra_flags=(), out: Path = None, tus=KERNEL_
     return lib
 
 
-def kernel_resources(tag: str = "default", auxiliary: bool = False) -> dict:
+def kernel_resources(tag: str = "default", auxiliary=False) -> dict:
     """what the last build of `tag` recorded (see parse_kernel_resources) for the solver's kernel families, or
-    (`auxiliary`) for the families of AUXILIARY_TUS"""
+    (`auxiliary` True) for the families of AUXILIARY_TUS, or (`auxiliary` a name) for that group of NAMED_TUS"""
     import json
     p = OBJ_DIR / tag / "kernel_resources.json"
     rec = json.loads(p.read_text()) if p.exists() else {}
     # (the record accumulates over builds: entries of translation units that no longer exist are dropped)
-    live = {"kernels_%d.o" % k for k in KERNEL_TUS if (k in AUXILIARY_TUS) == auxiliary}
+    named = {k for tus in NAMED_TUS.values() for k in tus}
+    if isinstance(auxiliary, str):
+        live = {"kernels_%d.o" % k for k in NAMED_TUS[auxiliary]}
+    else:
+        live = {"kernels_%d.o" % k for k in KERNEL_TUS if k not in named and (k in AUXILIARY_TUS) == auxiliary}
     return {k: v for k, v in rec.items() if v.get("object") in live}
 
 
@@ -291,6 +299,9 @@ def freeze_kernel_resources():
     p.write_text(json.dumps(out, indent=1, sort_keys=True))
     aux = {k: {f: v[f] for f in keep if f in v} for k, v in sorted(kernel_resources(auxiliary=True).items()) if k.startswith("pqp_")}
     (p.parent / "eig_kernel_resources_expected.json").write_text(json.dumps(aux, indent=1, sort_keys=True))
+    for name in NAMED_TUS:
+        grp = {k: {f: v[f] for f in keep if f in v} for k, v in sorted(kernel_resources(auxiliary=name).items()) if k.startswith("pqp_")}
+        (p.parent / ("%s_kernel_resources_expected.json" % name)).write_text(json.dumps(grp, indent=1, sort_keys=True))
     return p
 
 

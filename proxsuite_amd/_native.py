@@ -63,7 +63,8 @@ class NativeLib:
                "pqp_multi_solve_async", "pqp_multi_solve_range_async", "pqp_multi_wait", "pqp_multi_get_results",
                "pqp_multi_gather_device", "pqp_multi_get_trace", "pqp_multi_last_solve_ms", "pqp_box_calibrate",
                "pqp_batch_host_results_fresh_range", "pqp_batch_init_eig", "pqp_batch_update_eig", "pqp_multi_init_eig",
-               "pqp_multi_update_eig", "pqp_estimate_min_eigenvalues")
+               "pqp_multi_update_eig", "pqp_estimate_min_eigenvalues", "pqp_batch_backward_multi",
+               "pqp_batch_backward_multi_subset")
 
     def __init__(self, path, legacy=False):
         """legacy=True (A/B scripts only): an older build of the library that lacks the newer entries can still be
@@ -121,6 +122,9 @@ class NativeLib:
         L.pqp_batch_host_results_fresh.argtypes = [vp, C.c_int64]
         L.pqp_batch_own_stream.argtypes = [vp]
         L.pqp_batch_backward_subset.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64, _DP] + [C.c_double] * 3
+        L.pqp_batch_backward_multi.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, _DP] + [C.c_double] * 3 + [_DP, C.POINTER(C.c_int32)]
+        L.pqp_batch_backward_multi_subset.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64, C.c_int64, _DP] + [C.c_double] * 3 + \
+            [_DP, C.POINTER(C.c_int32)]
         L.pqp_multi_create.argtypes = [C.c_int64] * 4 + [C.c_int] * 3 + [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
         L.pqp_multi_destroy.argtypes = [vp]
         L.pqp_multi_destroy.restype = None
@@ -489,6 +493,57 @@ class Batch:
         k, p = _as_array(loss_derivatives, (len(ii), ntot), "loss_derivatives")
         self.lib.check(self.lib.L.pqp_batch_backward_subset(self._h, ii.ctypes.data_as(C.POINTER(C.c_int64)), len(ii), p,
                                                             float(eps), float(rho_backward), float(mu_backward)))
+
+    def backward_multi(self, loss_derivatives, eps=1e-4, rho_backward=1e-6, mu_backward=1e-6, first=None, count=None,
+                       idx=None, into=None):
+        """pqp_batch_backward_multi(_subset): compute_backward's linear solve for K loss derivatives per QP in one launch,
+        the factorisation done once per QP.  `loss_derivatives`: [rows, K, n + n_eq + n_in] (numpy or torch, host or
+        ROCm), rows = B, or `count` from `first`, or len(idx) (slot i belongs to QP idx[i]).  Returns (V, active) where
+        the input lives: V [rows, K, n + n_eq + n_in] holds the rows (V_x, V_y, V_z) the jacobians are made of, active
+        [rows, n_in] int32 the flags (bit 0: active from above, bit 1: from below).  `into=(V, active)` fills the
+        caller's buffers of the same kind instead."""
+        ntot = self.n + self.n_eq + self.n_in
+        ii = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
+        if ii is not None:
+            first, rows = 0, len(ii)
+        elif first is None:
+            first, rows = 0, self.B
+        else:
+            rows = int(1 if count is None else count)
+        is_torch = hasattr(loss_derivatives, "data_ptr")
+        if is_torch:
+            import torch
+            ld = loss_derivatives.detach()
+            if ld.dtype != torch.float64 or not ld.is_contiguous():
+                ld = ld.to(torch.float64).contiguous()
+        else:
+            ld = np.ascontiguousarray(np.asarray(loss_derivatives, dtype=np.float64))
+        if len(ld.shape) != 3 or tuple(ld.shape[::2]) != (rows, ntot):
+            raise ValueError("wrong argument size: loss_derivatives has shape %s, expected (%d, K, %d)"
+                             % (tuple(ld.shape), rows, ntot))
+        K = int(ld.shape[1])
+        if into is not None:
+            V, act = into
+        elif is_torch:
+            V = torch.zeros((rows, K, ntot), dtype=torch.float64, device=ld.device)
+            act = torch.zeros((rows, self.n_in), dtype=torch.int32, device=ld.device)
+        else:
+            V, act = np.zeros((rows, K, ntot)), np.zeros((rows, self.n_in), dtype=np.int32)
+        for name, buf, shape in (("V", V, (rows, K, ntot)), ("active", act, (rows, self.n_in))):
+            ok = (buf.is_contiguous() if hasattr(buf, "data_ptr") else buf.flags["C_CONTIGUOUS"]) and tuple(buf.shape) == shape
+            if not ok or hasattr(buf, "data_ptr") != is_torch or (is_torch and buf.device != ld.device):
+                raise ValueError("backward_multi: %s must be contiguous, of shape %s and live where loss_derivatives lives"
+                                 % (name, shape))
+        if is_torch and ld.is_cuda:
+            torch.cuda.current_stream(ld.device).synchronize()  # (the entry runs on the handle's stream and is synchronous)
+        ptr = (lambda t: t.data_ptr()) if is_torch else (lambda a: a.ctypes.data)
+        args = (K, C.cast(ptr(ld), _DP), float(eps), float(rho_backward), float(mu_backward), C.cast(ptr(V), _DP),
+                C.cast(ptr(act), C.POINTER(C.c_int32)))
+        if ii is not None:
+            self.lib.check(self.lib.L.pqp_batch_backward_multi_subset(self._h, ii.ctypes.data_as(C.POINTER(C.c_int64)), rows, *args))
+        else:
+            self.lib.check(self.lib.L.pqp_batch_backward_multi(self._h, int(first), rows, *args))
+        return V, act
 
     def set_stream(self, stream):
         """`stream`: a hipStream_t as int (e.g. torch.cuda.current_stream().cuda_stream) or None."""

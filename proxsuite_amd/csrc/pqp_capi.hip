@@ -67,6 +67,25 @@ dalloc(pqp_batch* h, T** p, size_t count)
   return PQP_OK;
 }
 
+// grow-only device buffer of the handle: at least `count` elements behind *p (its contents are not kept)
+template<typename T>
+int
+grow(pqp_batch* h, T** p, size_t* cap, size_t count)
+{
+  if (*p && *cap >= count)
+    return PQP_OK;
+  if (*p) {
+    h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), static_cast<void*>(*p)), h->allocs.end());
+    (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+  }
+  if (int rc = dalloc(h, p, count))
+    return rc;
+  *cap = count;
+  return PQP_OK;
+}
+
 int
 upload_settings(pqp_batch* h)
 {
@@ -1254,14 +1273,14 @@ pqp_batch_copy_qp(pqp_batch* dst, int64_t dst_idx, pqp_batch* src, int64_t src_i
   return PQP_OK;
 }
 
+// What every backward entry checks before it touches the device, in this order: the handle, the subset list (`order`
+// receives it) or the range, box constraints, the loss derivatives.
 static int
-backward_impl(pqp_batch* h, int64_t first, int64_t count, const int64_t* idx, const double* loss_derivatives,
-              double eps, double rho_backward, double mu_backward)
+backward_check(pqp_batch* h, int64_t first, int64_t count, const int64_t* idx, const double* loss_derivatives,
+               std::vector<int>& order)
 {
   if (!h)
     return fail(PQP_ERR_INVALID_ARGUMENT, "null batch handle");
-  const pqp::Dims& d = h->dev.d;
-  std::vector<int> order;
   if (idx) {
     if (count < 0 || count > h->dev.B)
       return fail(PQP_ERR_INVALID_ARGUMENT, "subset larger than the batch");
@@ -1277,42 +1296,58 @@ backward_impl(pqp_batch* h, int64_t first, int64_t count, const int64_t* idx, co
     }
   } else if (first < 0 || count < 0 || first + count > h->dev.B)
     return fail(PQP_ERR_INVALID_ARGUMENT, "backward range outside the batch");
-  if (h->vec_scratch)
-    return fail(PQP_ERR_UNSUPPORTED, "compute_backward is not built for shapes whose per-QP vectors exceed the LDS of a "
-                                     "CU (n + constraint rows above ~1100): the forward solve is");
-  if (d.box)
+  if (h->dev.d.box)
     return fail(PQP_ERR_UNSUPPORTED, "compute_backward is defined for QPs without box constraints "
                                      "(reference dense/compute_ECJ.hpp ignores them)");
   if (!loss_derivatives)
     return fail(PQP_ERR_INVALID_ARGUMENT, "loss_derivatives is required");
+  return PQP_OK;
+}
+
+// ... and once the handle is settled and its device current: queued commands run, and no QP of the launch may be dual
+// infeasible -- the reference throws for one (compute_ECJ.hpp:37-45)
+static int
+backward_ready(pqp_batch* h, int64_t first, int64_t count, const int64_t* idx)
+{
+  if (h->cmd_pending)
+    if (int rc = pqp_batch_flush(h))
+      return rc;
+  const size_t B = size_t(h->dev.B);
+  std::vector<pqp_info> info;
+  if (idx) {
+    std::vector<pqp_info> all(B);
+    HIP_TRY(hipMemcpy(all.data(), h->dev.info, B * sizeof(pqp_info), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < count; ++i)
+      info.push_back(all[size_t(idx[i])]);
+  } else {
+    info.resize(size_t(count));
+    HIP_TRY(hipMemcpy(info.data(), h->dev.info + first, size_t(count) * sizeof(pqp_info), hipMemcpyDeviceToHost));
+  }
+  for (int64_t i = 0; i < count; ++i)
+    if (info[size_t(i)].status == PQP_DUAL_INFEASIBLE)
+      return fail(PQP_ERR_INVALID_ARGUMENT,
+                  "the QP problem is not feasible, so computing the derivatives is not valid in this setting. "
+                  "Try enabling infeasible solving if the problem is only primally infeasible.");
+  return PQP_OK;
+}
+
+static int
+backward_impl(pqp_batch* h, int64_t first, int64_t count, const int64_t* idx, const double* loss_derivatives,
+              double eps, double rho_backward, double mu_backward)
+{
+  std::vector<int> order;
+  if (int rc = backward_check(h, first, count, idx, loss_derivatives, order))
+    return rc;
   if (count == 0)
     return PQP_OK;
   if (int rc = settle(h))
     return rc;
   PQP_ON_DEVICE(h->device);
-  if (h->cmd_pending)
-    if (int rc = pqp_batch_flush(h))
-      return rc;
+  if (int rc = backward_ready(h, first, count, idx))
+    return rc;
+  const pqp::Dims& d = h->dev.d;
   const size_t B = size_t(h->dev.B), n = size_t(d.n), ne = size_t(d.n_eq), ni = size_t(d.n_in);
   const size_t ntot = n + ne + ni;
-  // the reference throws for a dual infeasible QP (compute_ECJ.hpp:37-45)
-  {
-    std::vector<pqp_info> info;
-    if (idx) {
-      std::vector<pqp_info> all(B);
-      HIP_TRY(hipMemcpy(all.data(), h->dev.info, B * sizeof(pqp_info), hipMemcpyDeviceToHost));
-      for (int64_t i = 0; i < count; ++i)
-        info.push_back(all[size_t(idx[i])]);
-    } else {
-      info.resize(size_t(count));
-      HIP_TRY(hipMemcpy(info.data(), h->dev.info + first, size_t(count) * sizeof(pqp_info), hipMemcpyDeviceToHost));
-    }
-    for (int64_t i = 0; i < count; ++i)
-      if (info[size_t(i)].status == PQP_DUAL_INFEASIBLE)
-        return fail(PQP_ERR_INVALID_ARGUMENT,
-                    "the QP problem is not feasible, so computing the derivatives is not valid in this setting. "
-                    "Try enabling infeasible solving if the problem is only primally infeasible.");
-  }
   if (!h->bw_dH) {
     int rc = 0;
     if ((rc = dalloc(h, &h->bw_dH, B * n * n)) || (rc = dalloc(h, &h->bw_dg, B * n)) ||
@@ -1344,11 +1379,115 @@ backward_impl(pqp_batch* h, int64_t first, int64_t count, const int64_t* idx, co
     h->order_valid = false;
     bw.order = h->d_order;
   }
-  int rc = pqp_launch_backward(h, bw, long(count));
-  if (rc)
+  int rc;
+  if (h->vec_scratch) {
+    // per-QP vectors in HBM: the K-row kernel's HBM form with one row per QP, then the seven jacobians from that row
+    if ((rc = grow(h, &h->bwm_out, &h->bwm_out_cap, size_t(count) * ntot)) ||
+        (rc = grow(h, &h->bwm_active, &h->bwm_active_cap, size_t(count) * ni)))
+      return rc;
+    pqp::BackwardMultiArgs m{};
+    m.ld = h->bw_ld;
+    m.eps = eps;
+    m.rho_new = rho_backward;
+    m.mu_new = mu_backward;
+    m.out = h->bwm_out;
+    m.active = h->bwm_active;
+    m.n_rhs = 1;
+    m.first = bw.first;
+    m.order = bw.order;
+    if ((rc = pqp_launch_backward_multi_hbm(h, m, long(count))) ||
+        (rc = pqp_launch_backward_outer(h, bw, h->bwm_out, h->bwm_active, long(count))))
+      return rc;
+  } else if ((rc = pqp_launch_backward(h, bw, long(count))))
     return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   return PQP_OK;
+}
+
+static int
+backward_multi_impl(pqp_batch* h, int64_t first, int64_t count, const int64_t* idx, int64_t n_rhs,
+                    const double* loss_derivatives, double eps, double rho_backward, double mu_backward, double* out,
+                    int32_t* active)
+{
+  std::vector<int> order;
+  if (int rc = backward_check(h, first, count, idx, loss_derivatives, order))
+    return rc;
+  if (!out)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "out is required");
+  if (n_rhs < 0)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "n_rhs is negative");
+  const pqp::Dims& d = h->dev.d;
+  const size_t ni = size_t(d.n_in), ntot = size_t(d.n) + size_t(d.n_eq) + ni;
+  // count * n_rhs * ntot doubles must be addressable
+  const size_t lim = std::numeric_limits<int64_t>::max() / sizeof(double);
+  if (count > 0 && n_rhs > 0 && ntot > 0 && (size_t(n_rhs) > lim / size_t(count) || size_t(count) * size_t(n_rhs) > lim / ntot))
+    return fail(PQP_ERR_INVALID_ARGUMENT, "count * n_rhs * (dim + n_eq + n_in) overflows");
+  if (count == 0 || n_rhs == 0)
+    return PQP_OK;
+  if (int rc = settle(h))
+    return rc;
+  PQP_ON_DEVICE(h->device);
+  if (int rc = backward_ready(h, first, count, idx))
+    return rc;
+  const size_t total = size_t(count) * size_t(n_rhs) * ntot, nflags = size_t(count) * ni;
+  // host arrays are staged through buffers of the handle; device (or pinned / managed) memory is used in place
+  const bool ld_in_place = pqp_device_readable(loss_derivatives), out_in_place = pqp_device_readable(out);
+  const bool active_in_place = !active || pqp_device_readable(active);
+  int rc = 0;
+  if (!ld_in_place) {
+    if ((rc = grow(h, &h->bwm_ld, &h->bwm_ld_cap, total)))
+      return rc;
+    HIP_TRY(hipMemcpy(h->bwm_ld, loss_derivatives, total * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (!out_in_place && (rc = grow(h, &h->bwm_out, &h->bwm_out_cap, total)))
+    return rc;
+  if (!active_in_place && (rc = grow(h, &h->bwm_active, &h->bwm_active_cap, nflags)))
+    return rc;
+  if ((rc = upload_settings(h)))
+    return rc;
+  pqp::BackwardMultiArgs m{};
+  m.ld = ld_in_place ? loss_derivatives : h->bwm_ld;
+  m.eps = eps;
+  m.rho_new = rho_backward;
+  m.mu_new = mu_backward;
+  m.out = out_in_place ? out : h->bwm_out;
+  m.active = active ? (active_in_place ? reinterpret_cast<int*>(active) : h->bwm_active) : nullptr;
+  m.n_rhs = long(n_rhs);
+  m.first = long(first);
+  m.order = nullptr;
+  if (idx) {
+    HIP_TRY(hipMemcpy(h->d_order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
+    h->order_valid = false;
+    m.order = h->d_order;
+  }
+  // (the epilogue rewrites Info of every QP of the launch: a host mirror of it no longer holds what the device holds)
+  for (int64_t i = 0; i < count; ++i)
+    mirror_stale(h, idx ? idx[i] : first + i);
+  if ((rc = h->vec_scratch ? pqp_launch_backward_multi_hbm(h, m, long(count)) : pqp_launch_backward_multi(h, m, long(count))))
+    return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (!out_in_place)
+    HIP_TRY(hipMemcpy(out, h->bwm_out, total * sizeof(double), hipMemcpyDeviceToHost));
+  if (!active_in_place && nflags)
+    HIP_TRY(hipMemcpy(active, h->bwm_active, nflags * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return PQP_OK;
+}
+
+int
+pqp_batch_backward_multi(pqp_batch* h, int64_t first, int64_t count, int64_t n_rhs, const double* loss_derivatives,
+                         double eps, double rho_backward, double mu_backward, double* out, int32_t* active)
+{
+  return backward_multi_impl(h, first, count, nullptr, n_rhs, loss_derivatives, eps, rho_backward, mu_backward, out, active);
+}
+
+int
+pqp_batch_backward_multi_subset(pqp_batch* h, const int64_t* idx, int64_t count, int64_t n_rhs,
+                                const double* loss_derivatives, double eps, double rho_backward, double mu_backward,
+                                double* out, int32_t* active)
+{
+  if (!h || (count > 0 && !idx))
+    return fail(PQP_ERR_INVALID_ARGUMENT, "null argument");
+  return backward_multi_impl(h, 0, count, idx, n_rhs, loss_derivatives, eps, rho_backward, mu_backward, out, active);
 }
 
 int

@@ -110,6 +110,11 @@ struct pqp_batch
   // QPLayer backward outputs ([B][...], allocated at the first pqp_batch_backward)
   double *bw_dH = nullptr, *bw_dg = nullptr, *bw_dA = nullptr, *bw_db = nullptr, *bw_dC = nullptr,
          *bw_du = nullptr, *bw_dl = nullptr, *bw_ld = nullptr;
+  // pqp_batch_backward_multi: staging of host arguments (grow-only; *_cap in elements) and the rows / flags of the
+  // n_rhs = 1 launch a vec_scratch handle's pqp_batch_backward is made of
+  double *bwm_ld = nullptr, *bwm_out = nullptr;
+  int* bwm_active = nullptr;
+  size_t bwm_ld_cap = 0, bwm_out_cap = 0, bwm_active_cap = 0;
   // Longest-processing-time-first dispatch (OFF by default, pqp_batch_set_schedule): after a
   // whole-batch solve the per-QP device cycle counts order the NEXT whole-batch solve of the same
   // handle, most expensive QP first.  QPs are independent, so the order changes nothing but the
@@ -179,6 +184,11 @@ int pqp_launch_setup(pqp_batch* h);
 LaunchPlan pqp_plan_solve(const pqp_batch* h, long first, long count, const std::vector<int>* subset);
 int pqp_launch_solve(pqp_batch* h); // plans the launch h->range_* / h->subset_* describe, times and enqueues it
 int pqp_launch_backward(pqp_batch* h, const pqp::BackwardArgs& bw, long count);
+// K loss derivatives per QP (Solver::backward_multi): the LDS form by h->nt, the form of the handles whose vectors live in
+// h->vec_scratch, and the element-wise kernel that forms the outputs of `bw` from one row per QP (v: [count][ntot])
+int pqp_launch_backward_multi(pqp_batch* h, const pqp::BackwardMultiArgs& bw, long count);
+int pqp_launch_backward_multi_hbm(pqp_batch* h, const pqp::BackwardMultiArgs& bw, long count);
+int pqp_launch_backward_outer(pqp_batch* h, const pqp::BackwardArgs& bw, const double* v, const int* active, long count);
 int pqp_launch_order(pqp_batch* h, long count);
 int pqp_launch_pack(pqp_batch* h, long first, long count, double* out, hipStream_t stream);
 

@@ -285,6 +285,22 @@ struct BackwardArgs
   const int* order; // optional (pqp_batch_backward_subset): workgroup i works on QP order[i]; row i of `ld` is its loss derivative
 };
 
+// The same backward pass for `n_rhs` loss derivatives per QP in one launch (Solver::backward_multi): the active set, the
+// factorisation at (rho_new, mu_new) and the Schur block depend on the solved QP only, so they are done once and the
+// refined KKT solve is repeated per row.  `ld` and `out` are [count][n_rhs][n + n_eq + n_in] (slot-major: row k of
+// workgroup i); a row of `out` is the unscaled (dx, dy, dz) the seven jacobians of BackwardArgs are formed from.
+// `active` (optional) is [count][n_in]: bit 0 = the constraint is active from above, bit 1 = from below.
+struct BackwardMultiArgs
+{
+  const double* ld;
+  double eps, rho_new, mu_new;
+  double* out;
+  int* active;
+  long n_rhs;
+  long first;
+  const int* order; // optional: workgroup i works on QP order[i]
+};
+
 // LDS carve-up -------------------------------------------------------------------------
 // The ~45 per-QP vectors are grouped by length class (n, n_eq, n_c, n_in, n_d) so that every
 // LDS address is  base + (slot * class_length + class_offset)  : twelve scalars describe the
@@ -4925,7 +4941,145 @@ struct Solver
       Ww.dirty = 1;
     }
   }
+
+  // ---- backward() for bw.n_rhs loss derivatives of one QP: everything up to apply_active_set() once, then per row the
+  // right-hand side, the refined KKT solve and the unscaling of backward(), statement for statement (the two quirks of
+  // the reference included), the rows one after the other through the same iterative_solve -- a row's arithmetic is that
+  // of a single-row call.  The outer products are left to the caller (pqp_backward_outer_kernel forms them from a row);
+  // row k goes to out[slot][k][:] as (dx_u, dy_u, dz_u).  The state epilogue is backward()'s, once per QP.
+  __device__ __forceinline__ void backward_multi(const BackwardMultiArgs& bw, long slot_in_launch)
+  {
+    const int n = d.n, ne = d.n_eq, ni = d.n_in;
+    const long ntot = (long)n + ne + ni;
+    for (int k = threadIdx.x; k < ST_COUNT; k += NT)
+      L.stat()[k] = 0;
+    {
+      const State& Wr = *P.state();
+      diag_mode = (SPEC == 0) && d.hessian != PQP_HESSIAN_DENSE && d.n_eq == 0 && Wr.c_diag != 0 &&
+                  !(d.n_in > 0 && d.box != 0);
+      ruiz_c = Wr.ruiz_c;
+    }
+    info.load(*P.info());
+    const double c = ruiz_c;
+    vload(L.x(), P.x(), n);
+    vload(L.y(), P.y(), ne);
+    vload(L.z(), P.z(), ni);
+    cgptr dX = P.dlt_x(), dE = P.dlt_eq(), dI = P.dlt_in();
+    for (int k = threadIdx.x; k < n; k += NT)
+      L.dx()[k] = P.x()[k] / dX[k]; // x in the equilibrated space
+    for (int i = threadIdx.x; i < ni; i += NT) {
+      L.aflags()[i] = 0;
+      L.slot_of()[i] = -1;
+    }
+    __syncthreads();
+    // active sets at the solution (compute_ECJ.hpp:48-57):  C x + z - u >= 0,  C x + z - l <= 0
+    if (ni > 0) {
+      if (dm()) {
+        cgptr cd = P.CTs();
+        for (int i = threadIdx.x; i < ni; i += NT)
+          L.Cdx()[i] = cd[i] * L.dx()[i];
+        __syncthreads();
+      } else {
+        mv(P.CTs(), ni, n, ni, L.dx(), L.Cdx());
+      }
+      cgptr gu = P.u(), gl = P.l();
+      for (int i = threadIdx.x; i < ni; i += NT) {
+        const double ctz = L.Cdx()[i] / dI[i] + L.z()[i];
+        const bool up = (ctz - gu[i]) >= 0., lo = (ctz - gl[i]) <= 0.;
+        L.aflags()[i] = (up ? 1 : 0) | (lo ? 2 : 0) | ((up || lo) ? 4 : 0);
+      }
+      __syncthreads();
+    }
+    info.rho = bw.rho_new;
+    info.mu_eq = bw.mu_new;
+    info.mu_in = bw.mu_new;
+    // setup_factorization + active_set_change from the empty set (:66-86)
+    factor_primal_block<false>();
+    n_c = 0;
+    n_slots = 0;
+    r = ne;
+    schur_dirty = true;
+    apply_active_set();
+    const int na = n_c;
+    for (long row = 0; row < bw.n_rhs; ++row) {
+      cgptr ld = (cgptr)(bw.ld + (slot_in_launch * bw.n_rhs + row) * ntot);
+      gptr o = (gptr)(bw.out + (slot_in_launch * bw.n_rhs + row) * ntot);
+      // right-hand side (:88-112)
+      for (int k = threadIdx.x; k < n; k += NT)
+        L.rx()[k] = -ld[k] * (dX[k] * c);
+      for (int k = threadIdx.x; k < ne; k += NT)
+        L.rd()[k] = -ld[n + k] * dE[k];
+      double in_any = 0.0;
+      for (int i = threadIdx.x; i < ni; i += NT)
+        in_any = fmax(in_any, fabs(ld[n + ne + i]));
+      in_any = R.max(in_any);
+      for (int i = threadIdx.x; i < ni; i += NT) {
+        const int a = L.slot_of()[i];
+        if (a >= 0) {
+          double v = 0.0;
+          if (in_any != 0.0) {
+            // written at loop iteration i of the reference, then scaled by delta_in[position a]
+            // at iterations i, i+1, ..., n_in-1
+            v = -ld[n + ne + i];
+            const double s = dI[a];
+            for (int t = i; t < ni; ++t)
+              v *= s;
+          }
+          L.rd()[ne + a] = v;
+        }
+      }
+      __syncthreads();
+      (void)iterative_solve(bw.eps);
+      // compute_backward_loss_ESG (:134-189): unpermute dz, unscale; each lane writes what it computed
+      for (int k = threadIdx.x; k < n; k += NT)
+        o[k] = L.dx()[k] * dX[k];
+      for (int k = threadIdx.x; k < ne; k += NT)
+        o[n + k] = L.sd()[k] * dE[k] / c;
+      for (int j = threadIdx.x; j < ni; j += NT) {
+        const int a = L.slot_of()[j];
+        double v;
+        if (a >= 0) {
+          v = L.sd()[ne + a];
+        } else {
+          // permuted position of an inactive constraint after active_set_change from the identity
+          // map: j + #{active i > j}
+          int before = 0;
+          for (int t = 0; t < na; ++t)
+            before += (L.act()[t] < j) ? 1 : 0;
+          v = ld[n + ne + (j + na - before)];
+        }
+        o[n + ne + j] = v * dI[j] / c;
+      }
+      __syncthreads(); // (the next row rewrites the right-hand side and the solution)
+    }
+    {
+      PQP_GLOBAL int* ga = P.act();
+      PQP_GLOBAL int* fl = (PQP_GLOBAL int*)(bw.active ? bw.active + slot_in_launch * ni : nullptr);
+      for (int i = threadIdx.x; i < ni; i += NT) {
+        ga[i] = act_pack(act_cid(ga[i]), L.aflags()[i]);
+        if (fl)
+          fl[i] = L.aflags()[i] & 3;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      info.store(*P.info());
+      State& Ww = *P.state();
+      Ww.factor_valid = 0;
+      Ww.primal_valid = 0; // (the block in HBM was factorised at rho_new)
+      Ww.ls_valid = 0;
+      Ww.dirty = 1;
+    }
+  }
 };
+
+template<int NT>
+__device__ __forceinline__ void
+backward_multi_body(const Batch& batch, const BackwardMultiArgs& bw, long slot, lptr lds_base)
+{
+  Solver<NT, 0> S(batch, bw.order ? (long)bw.order[slot] : bw.first + slot, lds_base);
+  S.backward_multi(bw, slot);
+}
 
 template<int NT>
 __device__ __forceinline__ void

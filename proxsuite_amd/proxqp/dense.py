@@ -11,6 +11,8 @@ expose-parallel.hpp:27-46, expose-solve.hpp) for the dense ProxQP path:
     solve_in_parallel(qps, num_threads=None)
     solve(H, g, A, b, C, l, u, ...)
     compute_backward(qp, loss_derivative, eps, rho_backward, mu_backward)   -> qp.model.backward_data
+    compute_backward_multi(qp, loss_derivatives[K, ntot], ...)              -> dict (K rows, one factorisation)
+    solution_jacobians(qp, ...)                                             -> dx_dg, dx_db, dx_du, dx_dl
     solve_backward_in_parallel(num_threads, qps, loss_derivatives, ...)
     estimate_minimal_eigen_value_of_symmetric_matrix(H, ...)               (host-side helper)
 
@@ -31,7 +33,7 @@ from .._ctypes_defs import (DenseBackend, EigenValueEstimateMethodOption, Hessia
                             MeritFunctionType, QPSolverOutput, pqp_info, pqp_settings)
 
 __all__ = ["QP", "BatchQP", "VectorQP", "VectorLossDerivatives", "solve_in_parallel", "solve", "solve_no_gil",
-           "compute_backward", "solve_backward_in_parallel", "estimate_minimal_eigen_value_of_symmetric_matrix",
+           "compute_backward", "compute_backward_multi", "solution_jacobians", "solve_backward_in_parallel", "estimate_minimal_eigen_value_of_symmetric_matrix",
            "EigenValueEstimateMethodOption", "DenseBackend", "HessianType", "InitialGuess",
            "QPSolverOutput", "MeritFunctionType", "Settings", "Results", "Info", "Model", "BackwardData"]
 
@@ -555,6 +557,40 @@ def compute_backward(qp, loss_derivative, eps=1e-4, rho_backward=1e-6, mu_backwa
     out = qp._pool.batch.backward_results(qp._slot)
     _store_backward(qp, {k: v[None] for k, v in out.items()}, 0)
     qp._pool.touch()
+
+
+def _rows_to_jacobians(V, active, n, ne):
+    """the vector-shaped jacobians of compute_backward_loss_ESG from rows (V_x, V_y, V_z) and the active flags"""
+    Vz = V[..., n + ne:]
+    up, low = (active & 1) != 0, (active & 2) != 0
+    return dict(dL_dg=V[..., :n].copy(), dL_db=-V[..., n:n + ne], dL_du=np.where(up, -Vz, 0.0), dL_dl=np.where(low, -Vz, 0.0))
+
+
+def compute_backward_multi(qp, loss_derivatives, eps=1e-4, rho_backward=1e-6, mu_backward=1e-6):
+    """compute_backward for K loss derivatives ([K, n + n_eq + n_in]) of one solved QP in one launch: the factorisation at
+    (rho_backward, mu_backward) is done once, the refined KKT solve per row.  Returns a dict: dL_dg [K, n], dL_db
+    [K, n_eq], dL_du / dL_dl [K, n_in], `vectors` [K, n + n_eq + n_in] (the rows (V_x, V_y, V_z) they are made of) and
+    `active` [n_in] (bit 0: active from above, bit 1: from below).  qp.model.backward_data is left alone."""
+    ld = np.ascontiguousarray(np.asarray(loss_derivatives, dtype=np.float64))
+    if ld.ndim != 2:
+        raise ValueError("wrong argument size: loss_derivatives has shape %s, expected [K, n + n_eq + n_in]" % (ld.shape,))
+    batch = qp._pool.batch
+    V, act = batch.backward_multi(ld[None], eps, rho_backward, mu_backward, first=qp._slot, count=1)
+    qp._pool.touch()
+    out = _rows_to_jacobians(V[0], act[0][None, :], batch.n, batch.n_eq)
+    out["vectors"], out["active"] = V[0], act[0]
+    return out
+
+
+def solution_jacobians(qp, eps=1e-4, rho_backward=1e-6, mu_backward=1e-6):
+    """The jacobians of the solution x of one solved QP wrt its vectors, in ONE call (K = n loss derivatives [I_n | 0]):
+    dx_dg [n, n], dx_db [n, n_eq], dx_du and dx_dl [n, n_in] -- row i is compute_backward's dL_dg ... for the loss x_i."""
+    batch = qp._pool.batch
+    n = batch.n
+    ld = np.zeros((n, n + batch.n_eq + batch.n_in))
+    ld[:, :n] = np.eye(n)
+    r = compute_backward_multi(qp, ld, eps, rho_backward, mu_backward)
+    return dict(dx_dg=r["dL_dg"], dx_db=r["dL_db"], dx_du=r["dL_du"], dx_dl=r["dL_dl"])
 
 
 def solve_backward_in_parallel(num_threads=None, qps=None, loss_derivatives=None, eps=1e-4, rho_backward=1e-6,

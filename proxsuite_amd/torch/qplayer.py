@@ -124,6 +124,29 @@ def _solve_batch(Q, p, A, b, G, l, u, eps, max_iter, infeasible):
     return lease, x, y, z, se, si
 
 
+def solution_jacobians(Q, p, A, b, G, l, u, eps=1e-9, maxIter=1000, eps_backward=1.0e-4, rho_backward=1.0e-6,
+                       mu_backward=1.0e-6):
+    """The solution of a batch of QPs and its jacobians wrt the vectors of the model: one forward solve with the settings
+    of QPFunction, then ONE backward launch with K = n loss derivatives per QP ([I_n | 0]: one factorisation per QP
+    instead of the n that a loop of autograd.grad calls over the components of x pays).  Returns
+    (x [B, n], dx/dp [B, n, n], dx/db [B, n, n_eq], dx/dl [B, n, n_in], dx/du [B, n, n_in]) on the inputs' device."""
+    nbatch = _extract_nbatch((Q, 3), (p, 2), (A, 3), (b, 2), (G, 3), (l, 2), (u, 2))
+    Q_, p_, G_ = _expand(Q, nbatch, 3), _expand(p, nbatch, 2), _expand(G, nbatch, 3)
+    u_, l_ = _expand(u, nbatch, 2), _expand(l, nbatch, 2)
+    A_, b_ = _expand(A, nbatch, 3), _expand(b, nbatch, 2)
+    lease, x, _, _, _, _ = _solve_batch(Q_, p_, A_, b_, G_, l_, u_, eps, maxIter, infeasible=False)
+    batch, dev = lease.batch, Q_.device
+    B, n, ne, ni = batch.B, batch.n, batch.n_eq, batch.n_in
+    ld = torch.zeros((B, n, n + ne + ni), dtype=torch.float64, device=dev)
+    ld[:, :, :n] = torch.eye(n, dtype=torch.float64, device=dev)
+    V, act = batch.backward_multi(ld, eps_backward, rho_backward, mu_backward)
+    Vz, zero = V[:, :, n + ne:], torch.zeros((), dtype=torch.float64, device=dev)
+    up, low = ((act & 1) != 0).unsqueeze(1), ((act & 2) != 0).unsqueeze(1)
+    t = Q.dtype
+    return (x.to(t), V[:, :, :n].to(t), (-V[:, :, n:n + ne]).to(t), torch.where(low, -Vz, zero).to(t),
+            torch.where(up, -Vz, zero).to(t))
+
+
 def QPFunction(eps=1e-9, maxIter=1000, eps_backward=1.0e-4, rho_backward=1.0e-6, mu_backward=1.0e-6,
                omp_parallel=False, structural_feasibility=True):
     """Factory with the reference's signature (qplayer.py:12-20).  `omp_parallel` is accepted and

@@ -227,7 +227,7 @@ VARIANT_DIR = CSRC / "variants"
 
 
 def build_hip_variants(force: bool = False):
-    """Register-budget variants of the 512-thread latency kernel (PQP_WPS_512 = 3 and 4; the product
+    """A/B partners that travel with the tree.  Register-budget variants of the 512-thread latency kernel (PQP_WPS_512 = 3 and 4; the product
     uses 2), for the GPU regression test that sweeps them (tests/test_gpu_parity.py): round 1 saw
     NaNs at (512, 4) with a kernel that has since been rewritten; the sweep keeps watch.  Only the
     translation unit of that kernel is recompiled; the other objects are the product's."""
@@ -241,6 +241,14 @@ def build_hip_variants(force: bool = False):
             compile_tu(3, o3, ("-DPQP_WPS_512=%d" % w,))
             link_hip(lib, replaced={"kernels_3.o": o3})
         out.append(lib)
+    # the one-wavefront dense kernel with the two-pass dual Schur solve / row append everywhere (PQP_DW_SCHUR_ONE_PASS=0,
+    # csrc/pqp_dwave.hpp): the A/B twin of the one-pass form, bit for bit the same results (tests/test_gpu_schur_one_pass.py)
+    lib = VARIANT_DIR / "libproxqp_hip_schur2pass.so"
+    if force or not _newer(lib, deps):
+        import json
+        _, res = build_tu_variant(17, ("-DPQP_DW_SCHUR_ONE_PASS=0",), lib)
+        (OBJ_DIR / "default" / "kernel_resources_schur2pass.json").write_text(json.dumps(res, indent=1, sort_keys=True))
+    out.append(lib)
     return out
 
 

@@ -42,6 +42,11 @@ namespace pqp {
 #ifndef PQP_DW_SCHUR_REG_BLOCKS
 #define PQP_DW_SCHUR_REG_BLOCKS 8
 #endif
+// the dual Schur solve and the row append read W_S once (r <= 128): row sums, t / D_S and column sums from the same loaded
+// rows (mat_pass_block's SELF mode).  0: two passes everywhere, the A/B twin (variants/libproxqp_hip_schur2pass.so)
+#ifndef PQP_DW_SCHUR_ONE_PASS
+#define PQP_DW_SCHUR_ONE_PASS 1
+#endif
 constexpr int DW_SCHUR_REG_BLOCKS = PQP_DW_SCHUR_REG_BLOCKS; // dual blocks of up to 16 x this many slots are factorised in registers
 constexpr int DW_MAXDIM = 128; // n, n_eq, n_in <= 128 (one register block each); slots n_eq + n_in <= 256 (two blocks)
 
@@ -341,7 +346,12 @@ struct DWave
   // Loads are BUFFER loads: lanes beyond the extent get zeros without a memory access and without a branch (dw_load_row).
   // LOW: row t's first used column is t (an upper triangular factor): lanes wholly left of it are pushed out of range too.
   // cvec must be zero beyond the length of the pass.
-  template<bool COLS, bool ROWS, int NCB, bool LOW>
+  // SELF (COLS and ROWS, NCB = 1): the coefficient of row t is its OWN row sum over d_t, and cvec hands in d (pair layout) --
+  // cacc += M^T D^{-1} M x from one read of M.  Per group of sixteen rows: loads, partial dots, reduction to rout as in
+  // any ROWS pass; then the owner lanes divide, and the rows -- still in their registers -- go into the column
+  // accumulators in the order of a COLS pass.  Same row sums, same division, same FMA chain per column as a ROWS pass
+  // followed by a COLS pass with c = rout / d: equal bits.
+  template<bool COLS, bool ROWS, int NCB, bool LOW, bool SELF = false>
   __device__ __forceinline__ void mat_pass_block(cgptr base, int kb, int t1, const int (&offv)[2], const int (&nrecv)[2],
                                                  const double (&cvec)[2], const double (&xop)[NCB][2], double (&cacc)[NCB][2],
                                                  lptr rout)
@@ -396,6 +406,35 @@ struct DWave
         }
       }
     };
+    // SELF: the two halves of `consume` apart -- the partial dots of eight rows ...
+    auto dots = [&](const DPair(&v)[8][NCB], double* p8) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        double pv = 0.0;
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb)
+          pv = fma(v[u][cb].x, xop[cb][0], fma(v[u][cb].y, xop[cb][1], pv));
+        p8[u] = pv;
+      }
+    };
+    // ... and the eight rows into the column accumulators with the coefficients cs (pair layout, this group's items)
+    auto cols = [&](const DPair(&v)[8][NCB], int tb, const double (&cs)[2]) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int t = tb + u;
+        const double c = wave_bcast(cs[u & 1], (t & 127) >> 1);
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb) {
+          if (u & 1) {
+            acc2[cb][0] = fma(c, v[u][cb].x, acc2[cb][0]);
+            acc2[cb][1] = fma(c, v[u][cb].y, acc2[cb][1]);
+          } else {
+            cacc[cb][0] = fma(c, v[u][cb].x, cacc[cb][0]);
+            cacc[cb][1] = fma(c, v[u][cb].y, cacc[cb][1]);
+          }
+        }
+      }
+    };
     auto reduce16 = [&](const double* p, int g) {
       pqp_d4 T;
 #pragma unroll
@@ -437,11 +476,32 @@ struct DWave
         for (int hb = 0; hb < HB; ++hb)
           issue(v[hb], g + h0 + 8 * hb);
         dw_sched_fence(); // every load of the batch is issued before the first use of one
+        if constexpr (SELF) {
+          static_assert(!SELF || (COLS && ROWS && NCB == 1 && HB >= 2), "SELF: one column block, whole groups loaded together");
 #pragma unroll
-        for (int hb = 0; hb < HB; ++hb)
-          consume(v[hb], g + h0 + 8 * hb, p + h0 + 8 * hb);
+          for (int hb = 0; hb < HB; ++hb)
+            dots(v[hb], p + 8 * hb);
+#pragma unroll
+          for (int k = 0; k < GR; k += 16)
+            if (g + k < hi_t)
+              reduce16(p + k, g + k);
+          __syncthreads(); // the group's row sums are in rout
+          double cs[2];
+          DW_S(s)
+          {
+            const int a = idx(s);
+            cs[s] = (a >= g && a < g + GR && a < hi_t) ? rout[a] / cvec[s] : 0.0;
+          }
+#pragma unroll
+          for (int hb = 0; hb < HB; ++hb)
+            cols(v[hb], g + 8 * hb, cs);
+        } else {
+#pragma unroll
+          for (int hb = 0; hb < HB; ++hb)
+            consume(v[hb], g + h0 + 8 * hb, p + h0 + 8 * hb);
+        }
       }
-      if (ROWS) {
+      if (ROWS && !SELF) {
 #pragma unroll
         for (int k = 0; k < GR; k += 16)
           if (g + k < hi_t)
@@ -527,11 +587,12 @@ struct DWave
       mat_pass_block<COLS, ROWS, NCB, false>(base, 1, t1, w.off[1], w.nrec[1], cvec[1], xop, cacc, rout);
   }
   // coefficient vector of up to 128 items
-  template<bool COLS, bool ROWS, int NCB, bool LOW = false>
+  // (SELF: cvec is the divisor d of mat_pass_block's self-coefficient mode)
+  template<bool COLS, bool ROWS, int NCB, bool LOW = false, bool SELF = false>
   __device__ __forceinline__ void mat_pass1(cgptr base, int t1, const Rows1& w, const double (&cvec)[2],
                                             const double (&xop)[NCB][2], double (&cacc)[NCB][2], lptr rout)
   {
-    mat_pass_block<COLS, ROWS, NCB, LOW>(base, 0, t1, w.off, w.nrec, cvec, xop, cacc, rout);
+    mat_pass_block<COLS, ROWS, NCB, LOW, SELF>(base, 0, t1, w.off, w.nrec, cvec, xop, cacc, rout);
   }
 
   // out = H_s v from the LOWER TRIANGLE of the symmetric H_s alone, one pass: the column sums of the rows' used parts
@@ -1106,6 +1167,19 @@ struct DWave
   {
     const int rr = r, ld = nd;
     cgptr W = P.WS();
+#if PQP_DW_SCHUR_ONE_PASS
+    if (rr <= 128) {
+      // one read of W_S: t = W v, t / D and W^T (t / D) per group of sixteen rows
+      const double xop[1][2] = { { v[0][0], v[0][1] } };
+      double acc[1][2] = { { 0.0, 0.0 } };
+      mat_pass1<true, true, 1, false, true>(W, rr, rows_tril(ld, rr), dS[0], xop, acc, scr);
+      __syncthreads();
+      DW_S(s) v[0][s] = (didx(0, s) < rr) ? acc[0][s] : 0.0;
+      DW_S(s) v[1][s] = 0.0;
+      bytes((long)rr * (rr + 1) * 4);
+      return;
+    }
+#endif
     double none[2][2] = { { 0.0, 0.0 }, { 0.0, 0.0 } };
     // t = W v (row sums)
     if (rr > 128)
@@ -1266,7 +1340,34 @@ struct DWave
     }
     const double scc = G[gid * ld + gid] + info.mu_in;
     double delta = scc;
-    if (rr > 0) {
+    bool one_pass = false;
+#if PQP_DW_SCHUR_ONE_PASS
+    one_pass = rr <= 128;
+    if (rr > 0 && one_pass) {
+      // one read of W_S: t = W g, t / D and u = W^T (t / D); delta from the row sums the pass leaves in scr, as below
+      const double xop[1][2] = { { gv[0][0], gv[0][1] } };
+      double a1[1][2] = { { 0.0, 0.0 } };
+      mat_pass1<true, true, 1, false, true>(W, rr, rows_tril(ld, rr), dS[0], xop, a1, scr);
+      __syncthreads();
+      double acc = 0.0;
+      DW_B(b) DW_S(s)
+      {
+        const int a = didx(b, s);
+        const double t = (a < rr) ? scr[a] : 0.0;
+        const double td = t / dS[b][s];
+        acc = fma(t, td, acc);
+      }
+      __syncthreads();
+      delta = scc - lane_sum(acc);
+      DW_S(s)
+      {
+        const int a = didx(0, s);
+        if (a < rr)
+          W[(long)rr * ld + a] = -a1[0][s];
+      }
+    }
+#endif
+    if (rr > 0 && !one_pass) {
       double none[2][2] = { { 0.0, 0.0 }, { 0.0, 0.0 } };
       if (rr > 128)
         mat_pass2<false, true, 2>(W, rr, rows2_tril(ld, rr), none, gv, none, scr);
@@ -1317,7 +1418,7 @@ struct DWave
     }
     n_slots += 1;
     r += 1;
-    bytes((long)rr * (rr + 1) * 8 + (long)rr * 16);
+    bytes((long)rr * (rr + 1) * (one_pass ? 4 : 8) + (long)rr * 16);
     count(ST_N_APPEND);
     __syncthreads();
     return delta > 0.0;

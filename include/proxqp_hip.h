@@ -208,6 +208,25 @@ int pqp_batch_backward_multi(pqp_batch* h, int64_t first, int64_t count, int64_t
 int pqp_batch_backward_multi_subset(pqp_batch* h, const int64_t* idx, int64_t count, int64_t n_rhs,
                                     const double* loss_derivatives, double eps, double rho_backward, double mu_backward,
                                     double* out, int32_t* active);
+/* The backward pass of the closest-feasible QPLayer (reference bindings/python/proxsuite/torch/qplayer.py:371-610) for
+ * the QPs first .. first + count - 1, SOLVED with primal_infeasibility_solving and single-sided inequalities (every l at
+ * -1e20, as the layer's forward states them).  `loss_derivatives` is [count][dim + 2 n_eq + 2 n_in], host or device
+ * memory: (dl/dx | dl/dy | dl/dz | dl/dse | dl/dsi) per QP.  Per QP the reference's linear system K w = r
+ * (n_row = dim + 2 n_in + 2 n_eq rows, n_col = 2 dim + 2 n_in + n_eq (+ dim when n_eq > 0) columns) is assembled on
+ * the device, from the handle's results and unscaled model, in the model arrays of an inner handle that this handle
+ * owns -- shape (n_col, n_row, 0), zero Hessian, primal_infeasibility_solving, eps_abs = eps, max_iter,
+ * default_rho = refactor_rho_threshold = rho (the reference: eps_backward, 10, 1e-3) -- and solved there as a QP; the
+ * seven jacobians of the single-sided QP go to the arrays of pqp_batch_get_backward (dL_dl = 0).  The range is
+ * processed in passes of at most qps_per_pass QPs (the size of the inner handle); 0: as many as 16 GiB hold
+ * (environment PQP_INFEAS_BACKWARD_BYTES: another budget in bytes), at least one.  `solution` (may be NULL, host or
+ * device) receives w, [count][n_col]; `flags` (may be NULL, host or device) [count][n_in]: bit 0 = P1
+ * (min(s, 0) + z >= 0), bit 1 = P2 (s <= 0), s = C x - u.  Synchronous.  The results, Info and factors of the QPs are
+ * left as they are.  PQP_ERR_INVALID_ARGUMENT: a range outside the batch, a dual infeasible QP, a QP of the range with
+ * an l above -1e20 (nothing is solved then); PQP_ERR_UNSUPPORTED: box constraints, or an inner shape beyond the
+ * engine's size limits; count == 0: PQP_OK, nothing is touched. */
+int pqp_batch_backward_closest_feasible(pqp_batch* h, int64_t first, int64_t count, const double* loss_derivatives,
+                                        double eps, double rho, int64_t max_iter, int64_t qps_per_pass, double* solution,
+                                        int32_t* flags);
 /* Model::backward_data (reference dense/backward_data.hpp:27-133) of QP idx (-1: the whole
  * batch, arrays [B][...]); row-major; any pointer may be NULL. */
 int pqp_batch_get_backward(pqp_batch* h, int64_t idx, double* dL_dH, double* dL_dg, double* dL_dA,

@@ -52,7 +52,7 @@ def build_randqp(force: bool = False) -> Path:
 # pqp_kernels.hip is compiled once per kernel family (see its header): every solve kernel is
 # ~350 KB of inlined code and takes about a minute of hipcc time, so the objects are built in
 # parallel and linked into one shared library.
-KERNEL_TUS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21)
+KERNEL_TUS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22)
 # families outside the solver (19: the eigenvalue estimates of pqp_eig.hpp): built and linked like the others, their
 # resources frozen in a record of their own (tests/golden/eig_kernel_resources_expected.json) -- the solver's frozen record
 # names the solver's kernels and no others
@@ -60,7 +60,9 @@ AUXILIARY_TUS = (19,)
 # ... and further groups of that kind, each with a frozen record of its own and selected by name
 # (kernel_resources(auxiliary="backward_multi")): 20 / 21, the backward pass for K loss derivatives per QP, in LDS and on
 # an HBM slice (tests/golden/backward_multi_kernel_resources_expected.json)
-NAMED_TUS = {"backward_multi": (20, 21)}
+# 22, the closest-feasible QPLayer's backward pass: the assembly of its linear systems and its jacobians (csrc/pqp_infeas.hpp,
+# tests/golden/infeas_backward_kernel_resources_expected.json)
+NAMED_TUS = {"backward_multi": (20, 21), "infeas_backward": (22,)}
 OBJ_DIR = ROOT / "build" / "obj"
 
 

@@ -64,7 +64,7 @@ class NativeLib:
                "pqp_multi_gather_device", "pqp_multi_get_trace", "pqp_multi_last_solve_ms", "pqp_box_calibrate",
                "pqp_batch_host_results_fresh_range", "pqp_batch_init_eig", "pqp_batch_update_eig", "pqp_multi_init_eig",
                "pqp_multi_update_eig", "pqp_estimate_min_eigenvalues", "pqp_batch_backward_multi",
-               "pqp_batch_backward_multi_subset")
+               "pqp_batch_backward_multi_subset", "pqp_batch_backward_closest_feasible")
 
     def __init__(self, path, legacy=False):
         """legacy=True (A/B scripts only): an older build of the library that lacks the newer entries can still be
@@ -125,6 +125,8 @@ class NativeLib:
         L.pqp_batch_backward_multi.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, _DP] + [C.c_double] * 3 + [_DP, C.POINTER(C.c_int32)]
         L.pqp_batch_backward_multi_subset.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64, C.c_int64, _DP] + [C.c_double] * 3 + \
             [_DP, C.POINTER(C.c_int32)]
+        L.pqp_batch_backward_closest_feasible.argtypes = [vp, C.c_int64, C.c_int64, _DP, C.c_double, C.c_double, C.c_int64,
+                                                          C.c_int64, _DP, C.POINTER(C.c_int32)]
         L.pqp_multi_create.argtypes = [C.c_int64] * 4 + [C.c_int] * 3 + [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
         L.pqp_multi_destroy.argtypes = [vp]
         L.pqp_multi_destroy.restype = None
@@ -544,6 +546,39 @@ class Batch:
         else:
             self.lib.check(self.lib.L.pqp_batch_backward_multi(self._h, int(first), rows, *args))
         return V, act
+
+    def backward_closest_feasible(self, loss_derivatives, eps=1e-4, rho=1e-3, max_iter=10, first=0, count=None,
+                                  qps_per_pass=0):
+        """pqp_batch_backward_closest_feasible: the backward pass of the closest-feasible QPLayer for the QPs first ..
+        first + count - 1 (default: to the end of the batch), solved with primal_infeasibility_solving and single-sided
+        inequalities.  `loss_derivatives`: [count, n + 2 n_eq + 2 n_in] (numpy or torch, host or ROCm), the rows
+        (dl/dx | dl/dy | dl/dz | dl/dse | dl/dsi).  The seven jacobians go to backward_results().  Returns (solution,
+        flags) where the input lives: solution [count, n_col] the solutions of the inner linear systems, flags
+        [count, n_in] int32 (bit 0: P1, bit 1: P2).  `qps_per_pass`: QPs solved at once (0: by the library's byte budget)."""
+        n, ne, ni = self.n, self.n_eq, self.n_in
+        rows = self.B - int(first) if count is None else int(count)
+        width, n_col = n + 2 * ne + 2 * ni, 2 * n + 2 * ni + ne + (n if ne else 0)
+        is_torch = hasattr(loss_derivatives, "data_ptr")
+        if is_torch:
+            import torch
+            ld = loss_derivatives.detach()
+            if ld.dtype != torch.float64 or not ld.is_contiguous():
+                ld = ld.to(torch.float64).contiguous()
+            sol = torch.zeros((max(rows, 0), n_col), dtype=torch.float64, device=ld.device)
+            flags = torch.zeros((max(rows, 0), ni), dtype=torch.int32, device=ld.device)
+            if ld.is_cuda:
+                torch.cuda.current_stream(ld.device).synchronize()  # (the entry runs on the handle's stream and is synchronous)
+        else:
+            ld = np.ascontiguousarray(np.asarray(loss_derivatives, dtype=np.float64))
+            sol, flags = np.zeros((max(rows, 0), n_col)), np.zeros((max(rows, 0), ni), dtype=np.int32)
+        if rows >= 0 and tuple(ld.shape) != (rows, width):
+            raise ValueError("wrong argument size: loss_derivatives has shape %s, expected (%d, %d)"
+                             % (tuple(ld.shape), rows, width))
+        ptr = (lambda t: t.data_ptr()) if is_torch else (lambda a: a.ctypes.data)
+        self.lib.check(self.lib.L.pqp_batch_backward_closest_feasible(
+            self._h, int(first), rows, C.cast(ptr(ld), _DP), float(eps), float(rho), int(max_iter), int(qps_per_pass),
+            C.cast(ptr(sol), _DP), C.cast(ptr(flags), C.POINTER(C.c_int32))))
+        return sol, flags
 
     def set_stream(self, stream):
         """`stream`: a hipStream_t as int (e.g. torch.cuda.current_stream().cuda_stream) or None."""

@@ -474,6 +474,7 @@ pqp_batch_destroy(pqp_batch* h)
   if (!h)
     return;
   (void)settle(h);
+  pqp_batch_destroy(h->inner);
   DeviceGuard guard_(h->device);
   for (void* p : h->host_allocs)
     (void)hipHostFree(p);
@@ -1331,6 +1332,23 @@ backward_ready(pqp_batch* h, int64_t first, int64_t count, const int64_t* idx)
   return PQP_OK;
 }
 
+// the arrays pqp_batch_get_backward serves ([B][...], allocated at the first backward call of the handle)
+static int
+backward_arrays(pqp_batch* h)
+{
+  if (h->bw_dH)
+    return PQP_OK;
+  const pqp::Dims& d = h->dev.d;
+  const size_t B = size_t(h->dev.B), n = size_t(d.n), ne = size_t(d.n_eq), ni = size_t(d.n_in);
+  int rc = 0;
+  if ((rc = dalloc(h, &h->bw_dH, B * n * n)) || (rc = dalloc(h, &h->bw_dg, B * n)) ||
+      (rc = dalloc(h, &h->bw_dA, B * ne * n)) || (rc = dalloc(h, &h->bw_db, B * ne)) ||
+      (rc = dalloc(h, &h->bw_dC, B * ni * n)) || (rc = dalloc(h, &h->bw_du, B * ni)) ||
+      (rc = dalloc(h, &h->bw_dl, B * ni)) || (rc = dalloc(h, &h->bw_ld, B * (n + ne + ni))))
+    return rc;
+  return PQP_OK;
+}
+
 static int
 backward_impl(pqp_batch* h, int64_t first, int64_t count, const int64_t* idx, const double* loss_derivatives,
               double eps, double rho_backward, double mu_backward)
@@ -1348,14 +1366,8 @@ backward_impl(pqp_batch* h, int64_t first, int64_t count, const int64_t* idx, co
   const pqp::Dims& d = h->dev.d;
   const size_t B = size_t(h->dev.B), n = size_t(d.n), ne = size_t(d.n_eq), ni = size_t(d.n_in);
   const size_t ntot = n + ne + ni;
-  if (!h->bw_dH) {
-    int rc = 0;
-    if ((rc = dalloc(h, &h->bw_dH, B * n * n)) || (rc = dalloc(h, &h->bw_dg, B * n)) ||
-        (rc = dalloc(h, &h->bw_dA, B * ne * n)) || (rc = dalloc(h, &h->bw_db, B * ne)) ||
-        (rc = dalloc(h, &h->bw_dC, B * ni * n)) || (rc = dalloc(h, &h->bw_du, B * ni)) ||
-        (rc = dalloc(h, &h->bw_dl, B * ni)) || (rc = dalloc(h, &h->bw_ld, B * ntot)))
-      return rc;
-  }
+  if (int rc = backward_arrays(h))
+    return rc;
   HIP_TRY(hipMemcpy(h->bw_ld, loss_derivatives, size_t(count) * ntot * sizeof(double), hipMemcpyDefault));
   if (int rc = upload_settings(h))
     return rc;
@@ -1513,6 +1525,134 @@ pqp_batch_backward(pqp_batch* h, const double* loss_derivatives, double eps, dou
   if (!h)
     return fail(PQP_ERR_INVALID_ARGUMENT, "null batch handle");
   return pqp_batch_backward_range(h, 0, h->dev.B, loss_derivatives, eps, rho_backward, mu_backward);
+}
+
+// bytes of device memory one QP of an inner handle of shape (n, n_eq, 0) takes: the matrices of pqp_batch_create (model,
+// equilibrated copies, primal block, Z, Gram and Schur blocks); the vectors are noise beside them
+static double
+inner_bytes_per_qp(double n, double ne)
+{
+  return 8.0 * (5.0 * n * n + 3.0 * ne * n + 2.0 * ne * n + 3.0 * ne * ne);
+}
+
+int
+pqp_batch_backward_closest_feasible(pqp_batch* h, int64_t first, int64_t count, const double* loss_derivatives, double eps,
+                                    double rho, int64_t max_iter, int64_t qps_per_pass, double* solution, int32_t* flags)
+{
+  std::vector<int> order;
+  if (int rc = backward_check(h, first, count, nullptr, loss_derivatives, order))
+    return rc;
+  if (qps_per_pass < 0)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "qps_per_pass is negative");
+  if (count == 0)
+    return PQP_OK;
+  if (int rc = settle(h))
+    return rc;
+  PQP_ON_DEVICE(h->device);
+  if (int rc = backward_ready(h, first, count, nullptr))
+    return rc;
+  const pqp::Dims& d = h->dev.d;
+  const size_t ni = size_t(d.n_in);
+  const int n_row = pqp::infeas_rows(d.n, d.n_eq, d.n_in), n_col = pqp::infeas_cols(d.n, d.n_eq, d.n_in);
+  // QPs per pass: the caller's, else what a byte budget holds (a policy constant, not a measurement: an inner QP of a
+  // (100, 50, 200) layer takes ~50 MB of model and factors, 2048 of them at once would take ~100 GB)
+  int64_t pass = qps_per_pass;
+  if (pass == 0) {
+    double budget = 16.0 * 1024.0 * 1024.0 * 1024.0;
+    if (const char* e = std::getenv("PQP_INFEAS_BACKWARD_BYTES"))
+      budget = std::atof(e);
+    const double fit = std::floor(budget / inner_bytes_per_qp(n_col, n_row));
+    pass = fit < 1.0 ? 1 : (fit > double(count) ? count : int64_t(fit));
+  }
+  pass = std::min(pass, count);
+  if (h->inner && h->inner->dev.B < pass) {
+    pqp_batch_destroy(h->inner);
+    h->inner = nullptr;
+  }
+  if (!h->inner)
+    // (a shape beyond the engine's size limits: PQP_ERR_UNSUPPORTED from here)
+    if (int rc = pqp_batch_create(pass, n_col, n_row, 0, 0, PQP_HESSIAN_ZERO, PQP_BACKEND_AUTOMATIC, h->device, &h->inner))
+      return rc;
+  pqp_batch* in = h->inner;
+  if (int rc = pqp_batch_set_stream(in, h->stream))
+    return rc;
+  // the reference's settings of the inner QP (qplayer.py:516-520); everything else at its default
+  for (auto& st : in->settings) {
+    pqp_settings_default(&st, in->backend);
+    st.primal_infeasibility_solving = 1;
+    st.eps_abs = eps;
+    st.max_iter = max_iter;
+    st.default_rho = rho;
+    st.refactor_rho_threshold = rho;
+  }
+  in->settings_dirty = true;
+  int rc = 0;
+  if ((rc = backward_arrays(h)) || (rc = grow(h, &h->inf_p2c, &h->inf_p2c_cap, size_t(pass) * ni)))
+    return rc;
+  if (!h->inf_finite_l && (rc = dalloc(h, &h->inf_finite_l, 1)))
+    return rc;
+  const bool ld_in_place = pqp_device_readable(loss_derivatives);
+  const bool flags_in_place = flags && pqp_device_readable(flags);
+  if (!ld_in_place) {
+    if ((rc = grow(h, &h->inf_ld, &h->inf_ld_cap, size_t(count) * size_t(n_row))))
+      return rc;
+    HIP_TRY(hipMemcpy(h->inf_ld, loss_derivatives, size_t(count) * size_t(n_row) * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (!flags_in_place && (rc = grow(h, &h->inf_flags, &h->inf_flags_cap, size_t(pass) * ni)))
+    return rc;
+  HIP_TRY(hipMemsetAsync(h->inf_finite_l, 0, sizeof(int), h->stream));
+  pqp::BackwardArgs bw{};
+  bw.dL_dH = h->bw_dH;
+  bw.dL_dg = h->bw_dg;
+  bw.dL_dA = h->bw_dA;
+  bw.dL_db = h->bw_db;
+  bw.dL_dC = h->bw_dC;
+  bw.dL_du = h->bw_du;
+  bw.dL_dl = h->bw_dl;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (int64_t done = 0; done < count; done += pass) {
+    const int64_t cnt = std::min(pass, count - done);
+    pqp::InfeasArgs a{};
+    a.ld = (ld_in_place ? loss_derivatives : h->inf_ld) + size_t(done) * size_t(n_row);
+    a.first = long(first + done);
+    a.count = long(cnt);
+    a.K = in->dev.A;
+    a.r = in->dev.b;
+    a.w = in->dev.x;
+    a.flags = flags_in_place ? reinterpret_cast<int*>(flags) + size_t(done) * ni : h->inf_flags;
+    a.p2c = h->inf_p2c;
+    a.finite_l = h->inf_finite_l;
+    a.check_first = long(first);
+    a.check_count = done == 0 ? long(count) : 0;
+    if ((rc = settle(in)) || (rc = pqp_launch_infeas_kkt(h, a)))
+      return rc;
+    if (done == 0) {
+      int finite_l = 0;
+      HIP_TRY(hipStreamSynchronize(h->stream));
+      HIP_TRY(hipMemcpy(&finite_l, h->inf_finite_l, sizeof(int), hipMemcpyDeviceToHost));
+      if (finite_l)
+        return fail(PQP_ERR_INVALID_ARGUMENT, "the closest-feasible backward is defined for single-sided inequalities: a QP "
+                                              "of the range has a lower bound above -1e20");
+    }
+    // QP::init on the model already in place (H = 0 and g = 0 since the handle was created: no array is given, nothing
+    // is copied), then the engine's ordinary set-up and solve
+    if (cnt == in->dev.B)
+      rc = pqp_batch_init(in, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nan, nan,
+                          nan, nan);
+    else
+      for (int64_t q = 0; q < cnt && !rc; ++q)
+        rc = pqp_batch_init(in, q, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nan, nan,
+                            nan, nan);
+    if (rc || (rc = pqp_batch_solve_range(in, 0, cnt)) || (rc = pqp_launch_infeas_grad(h, a, bw)))
+      return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (solution)
+      HIP_TRY(hipMemcpy(solution + size_t(done) * size_t(n_col), in->dev.x, size_t(cnt) * size_t(n_col) * sizeof(double),
+                        hipMemcpyDefault));
+    if (flags && !flags_in_place && ni)
+      HIP_TRY(hipMemcpy(flags + size_t(done) * ni, h->inf_flags, size_t(cnt) * ni * sizeof(int32_t), hipMemcpyDeviceToHost));
+  }
+  return PQP_OK;
 }
 
 int

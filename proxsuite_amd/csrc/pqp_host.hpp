@@ -19,6 +19,7 @@
 
 #include "proxqp_hip.h"
 #include "pqp_solver.hpp"
+#include "pqp_infeas.hpp"
 
 // max(n, n_eq + n_c) a batch may have (pqp_batch_create).  The reference has no size limit (dense/model.hpp:65-68); here the
 // persistent slot list packs constraint ids into 16 bits (pqp::act_pack) and the set-up kernel keeps 2 (n + n_eq + n_c)
@@ -115,6 +116,13 @@ struct pqp_batch
   double *bwm_ld = nullptr, *bwm_out = nullptr;
   int* bwm_active = nullptr;
   size_t bwm_ld_cap = 0, bwm_out_cap = 0, bwm_active_cap = 0;
+  // pqp_batch_backward_closest_feasible: the inner handle that solves the linear systems of a pass (shape
+  // (n_col, n_row, 0), zero Hessian; created at the first call, replaced by a larger one when a pass needs more slots,
+  // destroyed with this handle) and the per-pass buffers beside it (grow-only; *_cap in elements)
+  pqp_batch* inner = nullptr;
+  double *inf_ld = nullptr, *inf_p2c = nullptr;
+  int *inf_flags = nullptr, *inf_finite_l = nullptr;
+  size_t inf_ld_cap = 0, inf_p2c_cap = 0, inf_flags_cap = 0;
   // Longest-processing-time-first dispatch (OFF by default, pqp_batch_set_schedule): after a
   // whole-batch solve the per-QP device cycle counts order the NEXT whole-batch solve of the same
   // handle, most expensive QP first.  QPs are independent, so the order changes nothing but the
@@ -189,6 +197,10 @@ int pqp_launch_backward(pqp_batch* h, const pqp::BackwardArgs& bw, long count);
 int pqp_launch_backward_multi(pqp_batch* h, const pqp::BackwardMultiArgs& bw, long count);
 int pqp_launch_backward_multi_hbm(pqp_batch* h, const pqp::BackwardMultiArgs& bw, long count);
 int pqp_launch_backward_outer(pqp_batch* h, const pqp::BackwardArgs& bw, const double* v, const int* active, long count);
+// the closest-feasible backward (pqp_infeas.hpp): the linear systems of a pass into a.K / a.r, and the seven jacobians of
+// `bw` from the inner solution a.w
+int pqp_launch_infeas_kkt(pqp_batch* h, pqp::InfeasArgs a);
+int pqp_launch_infeas_grad(pqp_batch* h, pqp::InfeasArgs a, const pqp::BackwardArgs& bw);
 int pqp_launch_order(pqp_batch* h, long count);
 int pqp_launch_pack(pqp_batch* h, long first, long count, double* out, hipStream_t stream);
 

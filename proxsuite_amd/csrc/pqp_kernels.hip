@@ -58,6 +58,12 @@
 //                                     seven jacobians of pqp_batch_get_backward from one row of its output
 //  21  pqp_backward_multi_hbm_kernel<1024>  the same on a slice of the HBM scratch buffer per workgroup (as 9): the
 //                                     backward pass of the shapes whose per-QP vectors exceed the LDS
+//  22  pqp_infeas_kkt_kernel<256>     the backward pass of the closest-feasible QPLayer (pqp_infeas.hpp): the linear system of
+//                                     every QP of a pass, written into the model arrays of the inner handle that solves it;
+//                                     and pqp_infeas_grad_kernel<256>, the seven jacobians from the inner solution
+#if PQP_TU == 0 || PQP_TU == 22
+#define PQP_INFEAS_DEVICE 1 // (pqp_host.hpp includes pqp_infeas.hpp for the launchers' argument record: the kernels' bodies with it here)
+#endif
 #include "pqp_host.hpp"
 #include "pqp_dwave.hpp"
 #if PQP_TU == 0 || PQP_TU == 19
@@ -463,6 +469,44 @@ pqp_launch_backward_multi_hbm(pqp_batch* h, const pqp::BackwardMultiArgs& bw, lo
 {
   hipLaunchKernelGGL((pqp_backward_multi_hbm_kernel<1024>), dim3((unsigned)count), dim3(1024), 0, h->stream, h->dev, bw,
                      h->vec_scratch, (long)((h->lds_solve + 7) / 8));
+  HIP_TRY(hipGetLastError());
+  return PQP_OK;
+}
+#endif
+
+#if PQP_TU_HAS(22)
+template<int NT>
+__global__ __launch_bounds__(NT) void
+pqp_infeas_kkt_kernel(pqp::Batch batch, pqp::InfeasArgs a)
+{
+  pqp::infeas_kkt_body<NT>(batch, a);
+}
+
+template<int NT>
+__global__ __launch_bounds__(NT) void
+pqp_infeas_grad_kernel(pqp::Batch batch, pqp::InfeasArgs a, pqp::BackwardArgs bw)
+{
+  pqp::infeas_grad_body<NT>(batch, a, bw);
+}
+
+// (a.shares is set here: row tiles of K per slot, spread until the launch has a few workgroups per CU)
+int
+pqp_launch_infeas_kkt(pqp_batch* h, pqp::InfeasArgs a)
+{
+  const pqp::Dims& d = h->dev.d;
+  const long tiles = (pqp::infeas_rows(d.n, d.n_eq, d.n_in) + pqp::INFEAS_TILE - 1) / pqp::INFEAS_TILE;
+  a.shares = (int)std::min<long>(tiles, std::max<long>(1, (4L * h->n_cu + a.count - 1) / a.count));
+  hipLaunchKernelGGL((pqp_infeas_kkt_kernel<256>), dim3((unsigned)(a.count * a.shares)), dim3(256), 0, h->stream, h->dev, a);
+  HIP_TRY(hipGetLastError());
+  return PQP_OK;
+}
+
+int
+pqp_launch_infeas_grad(pqp_batch* h, pqp::InfeasArgs a, const pqp::BackwardArgs& bw)
+{
+  const long n = h->dev.d.n, rows = std::max<long>(n, std::max<long>(h->dev.d.n_eq, h->dev.d.n_in));
+  a.shares = (int)std::min<long>(64, std::max<long>(1, (rows * n + 255) / 256));
+  hipLaunchKernelGGL((pqp_infeas_grad_kernel<256>), dim3((unsigned)(a.count * a.shares)), dim3(256), 0, h->stream, h->dev, a, bw);
   HIP_TRY(hipGetLastError());
   return PQP_OK;
 }

@@ -12,6 +12,7 @@ expose-parallel.hpp:27-46, expose-solve.hpp) for the dense ProxQP path:
     solve(H, g, A, b, C, l, u, ...)
     compute_backward(qp, loss_derivative, eps, rho_backward, mu_backward)   -> qp.model.backward_data
     compute_backward_multi(qp, loss_derivatives[K, ntot], ...)              -> dict (K rows, one factorisation)
+    compute_backward_closest_feasible(qp, loss_derivative, ...)             -> qp.model.backward_data (closest-feasible QPs)
     solution_jacobians(qp, ...)                                             -> dx_dg, dx_db, dx_du, dx_dl
     solve_backward_in_parallel(num_threads, qps, loss_derivatives, ...)
     estimate_minimal_eigen_value_of_symmetric_matrix(H, ...)               (host-side helper)
@@ -33,7 +34,7 @@ from .._ctypes_defs import (DenseBackend, EigenValueEstimateMethodOption, Hessia
                             MeritFunctionType, QPSolverOutput, pqp_info, pqp_settings)
 
 __all__ = ["QP", "BatchQP", "VectorQP", "VectorLossDerivatives", "solve_in_parallel", "solve", "solve_no_gil",
-           "compute_backward", "compute_backward_multi", "solution_jacobians", "solve_backward_in_parallel", "estimate_minimal_eigen_value_of_symmetric_matrix",
+           "compute_backward", "compute_backward_multi", "compute_backward_closest_feasible", "solution_jacobians", "solve_backward_in_parallel", "estimate_minimal_eigen_value_of_symmetric_matrix",
            "EigenValueEstimateMethodOption", "DenseBackend", "HessianType", "InitialGuess",
            "QPSolverOutput", "MeritFunctionType", "Settings", "Results", "Info", "Model", "BackwardData"]
 
@@ -557,6 +558,19 @@ def compute_backward(qp, loss_derivative, eps=1e-4, rho_backward=1e-6, mu_backwa
     out = qp._pool.batch.backward_results(qp._slot)
     _store_backward(qp, {k: v[None] for k, v in out.items()}, 0)
     qp._pool.touch()
+
+
+def compute_backward_closest_feasible(qp, loss_derivative, eps=1e-4, rho=1e-3, max_iter=10):
+    """The backward pass of the closest-feasible QPLayer (reference bindings/python/proxsuite/torch/qplayer.py:371-610)
+    for one QP solved with settings.primal_infeasibility_solving and single-sided inequalities (every l at -1e20 or
+    below).  `loss_derivative`: [n + 2 n_eq + 2 n_in] = (dl/dx | dl/dy | dl/dz | dl/dse | dl/dsi).  Fills
+    qp.model.backward_data as compute_backward does (dL_dl = 0); returns (solution of the inner linear system, flags)."""
+    ld = np.ascontiguousarray(np.asarray(loss_derivative, dtype=np.float64)).reshape(1, -1)
+    sol, flags = qp._pool.batch.backward_closest_feasible(ld, eps, rho, max_iter, first=qp._slot, count=1)
+    out = qp._pool.batch.backward_results(qp._slot)
+    _store_backward(qp, {k: v[None] for k, v in out.items()}, 0)
+    qp._pool.touch()
+    return sol[0], flags[0]
 
 
 def _rows_to_jacobians(V, active, n, ne):

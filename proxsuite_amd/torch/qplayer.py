@@ -11,9 +11,16 @@ results are copied device-to-device into the output tensors.
 
 The backward pass (reference qplayer.py:172-253) is ONE pqp_batch_backward launch (the device
 form of dense/compute_ECJ.hpp's compute_backward for every QP of the batch) whose seven jacobians
-are copied device-to-device into the gradient tensors.  The closest-feasible variant
-(`structural_feasibility=False`) differentiates through the sparse backend in the reference
-(qplayer.py:371-552); that path is outside this repository's scope and raises.
+are copied device-to-device into the gradient tensors.
+
+The closest-feasible variant (`structural_feasibility=False`) differentiates through its sparse backend in the
+reference (qplayer.py:371-610): per QP a rectangular linear system K w = r, solved as a QP with zero Hessian, K as
+equality constraints and primal_infeasibility_solving.  That QP is dense and of the kind this engine solves, so here the
+backward is ONE pqp_batch_backward_closest_feasible call: a kernel assembles K and r of every QP in the model arrays of
+an inner batch handle, the engine solves them, a second kernel forms the jacobians (csrc/pqp_infeas.hpp, DESIGN.md
+section 3g).  Three departures from the reference's Python, decided by the chain rule and by finite differences:
+dG = dG1[n_in:] - dG1[:n_in] of the single-sided G1 = [-G; G] (the reference keeps one half), parameters shared by the
+batch receive the SUM of the per-QP gradients (the reference: the mean), and everything stays in fp64.
 """
 from __future__ import annotations
 
@@ -214,6 +221,15 @@ def QPFunction(eps=1e-9, maxIter=1000, eps_backward=1.0e-4, rho_backward=1.0e-6,
             lo = torch.full_like(h, -1.0e20)
             lease, x, y, z, se, si = _solve_batch(Q, p, A, b, G1, lo, h, eps, maxIter, infeasible=True)
             ctx.lease = lease
+            ctx.batch = lease.batch  # (its result arrays are the inputs of the backward)
+            ctx.n_in = int(n_in)
+            ctx.dev = Q.device
+            ctx.dtype = Q.dtype
+            ctx.shapes = tuple(tuple(t_.shape) if t_.numel() else () for t_ in (Q_, p_, A_, b_, G_, l_, u_))
+            ctx.batched = (Q_.ndimension() == 3, p_.ndimension() == 2, A_.ndimension() == 3, b_.ndimension() == 2,
+                           G_.ndimension() == 3, l_.ndimension() == 2, u_.ndimension() == 2)
+            # the active half of every double-sided row (reference qplayer.py:480)
+            ctx.active = (-z[:, :n_in] + z[:, n_in:]) >= 0
             nus_sol = -z[:, :n_in] + z[:, n_in:]
             s_i = -si[:, :n_in] + si[:, n_in:]
             t = Q.dtype
@@ -221,8 +237,49 @@ def QPFunction(eps=1e-9, maxIter=1000, eps_backward=1.0e-4, rho_backward=1.0e-6,
 
         @staticmethod
         def backward(ctx, dl_dzhat, dl_dlams, dl_dnus, dl_ds_e, dl_ds_i):
-            raise NotImplementedError(
-                "the backward of the closest-feasible QPFunction differentiates through the sparse backend in "
-                "the reference (qplayer.py:371-552), which is outside this repository's scope")
+            batch, dev, ns = ctx.batch, ctx.dev, ctx.n_in
+            B, n, ne, ni = batch.B, batch.n, batch.n_eq, batch.n_in  # (ni = 2 ns: the single-sided QP)
+            # rows (dl/dx | dl/dlam | dl/dnu | dl/dse | dl/dsi) of the single-sided QP; the kernel negates them into the
+            # right-hand side, which then equals the reference's (qplayer.py:473-503): a double-sided derivative goes to
+            # the first half (-G) where the row is not active from above, negated, and to the second half where it is
+            ld = torch.zeros((B, n + 2 * ne + 2 * ni), dtype=torch.float64, device=dev)
+            act = ctx.active
+
+            def halves(at, v):
+                v = v.to(torch.float64)
+                zero = torch.zeros((), dtype=torch.float64, device=dev)
+                ld[:, at:at + ns] = torch.where(act, zero, -v)
+                ld[:, at + ns:at + ni] = torch.where(act, v, zero)
+
+            if dl_dzhat is not None:
+                ld[:, :n] = dl_dzhat
+            if dl_dlams is not None and ne:
+                ld[:, n:n + ne] = dl_dlams
+            if dl_dnus is not None and ni:
+                halves(n + ne, dl_dnus)
+            if dl_ds_e is not None and ne:
+                ld[:, n + ne + ni:n + 2 * ne + ni] = dl_ds_e
+            if dl_ds_i is not None and ni:
+                halves(n + 2 * ne + ni, dl_ds_i)
+            batch.backward_closest_feasible(ld, eps_backward)
+            opts = dict(dtype=torch.float64, device=dev)
+            out = dict(dL_dH=torch.empty((B, n, n), **opts), dL_dg=torch.empty((B, n), **opts),
+                       dL_dA=torch.empty((B, ne, n), **opts), dL_db=torch.empty((B, ne), **opts),
+                       dL_dC=torch.empty((B, ni, n), **opts), dL_du=torch.empty((B, ni), **opts))
+            batch.backward_results(-1, into=out)
+            # back to the double-sided parameters: G1 = [-G; G], h = [-l; u]
+            dC, du1 = out["dL_dC"], out["dL_du"]
+            grads = (out["dL_dH"], out["dL_dg"], out["dL_dA"], out["dL_db"], dC[:, ns:] - dC[:, :ns], -du1[:, :ns],
+                     du1[:, ns:])
+            t = ctx.dtype
+
+            def shaped(g, like_batched, shape):
+                if g.numel() == 0 or len(shape) == 0:
+                    return None
+                # parameters shared by the batch receive the sum of the per-QP gradients
+                return (g if like_batched else g.sum(dim=0)).to(t).reshape(shape)
+
+            bt, sh = ctx.batched, ctx.shapes
+            return tuple(shaped(g, bt[i], sh[i]) for i, g in enumerate(grads))
 
     return QPFunctionFn.apply if structural_feasibility else QPFunctionFn_infeas.apply

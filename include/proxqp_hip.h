@@ -208,6 +208,30 @@ int pqp_batch_backward_multi(pqp_batch* h, int64_t first, int64_t count, int64_t
 int pqp_batch_backward_multi_subset(pqp_batch* h, const int64_t* idx, int64_t count, int64_t n_rhs,
                                     const double* loss_derivatives, double eps, double rho_backward, double mu_backward,
                                     double* out, int32_t* active);
+/* The backward pass of QPs WITH box constraints (a handle created with box_constraints = 1; the entries above answer
+ * PQP_ERR_UNSUPPORTED for one).  The constraint list is [C; I]: n_c = n_in + dim rows, z = [z_in; z_box], and
+ * compute_backward + compute_backward_loss_ESG run over those rows in that order (the scaling vector of the inequality
+ * part is [delta_in; delta_box]) -- with identity equilibration the result is that of compute_backward on the same QP
+ * stated with the dim bounds as rows n_in .. n_in + dim - 1 of C.  `loss_derivatives` and `out` are
+ * [count][n_rhs][dim + n_eq + n_in + dim] = (dL/dx | dL/dy | dL/dz_in | dL/dz_box), host or device memory; row k of
+ * `out` is V = (V_x, V_y, V_zin, V_zbox).  `active` is [count][n_in + dim]; for a box row bit 0 is set when
+ * x_k + z_box_k - u_box_k >= 0, bit 1 when x_k + z_box_k - l_box_k <= 0.  `out` and `active` may be NULL.  With
+ * n_rhs == 1 the call also fills the arrays of pqp_batch_get_backward (dL_dC over the n_in general rows: the identity
+ * block has no parameter) and those of pqp_batch_get_backward_box: dL_du_box = -V_zbox where the row is active from above
+ * (else 0), dL_dl_box = -V_zbox where it is active from below; with n_rhs > 1 those arrays are not touched.  A QP of the
+ * handle initialised without bounds has them at +-infinity and no active box row.  Synchronous.  Errors and no-ops as
+ * pqp_batch_backward_multi; a handle without box constraints: PQP_ERR_INVALID_ARGUMENT (pqp_batch_backward,
+ * pqp_batch_backward_range / _subset and pqp_batch_backward_multi / _multi_subset serve it).  The QPs' state afterwards is
+ * that after pqp_batch_backward_range, the active flags of all n_c rows written back for the next solve. */
+int pqp_batch_backward_box(pqp_batch* h, int64_t first, int64_t count, int64_t n_rhs, const double* loss_derivatives,
+                           double eps, double rho_backward, double mu_backward, double* out, int32_t* active);
+/* ... on the `count` QPs idx[0..count): slot i of loss_derivatives / out / active belongs to QP idx[i] */
+int pqp_batch_backward_box_subset(pqp_batch* h, const int64_t* idx, int64_t count, int64_t n_rhs,
+                                  const double* loss_derivatives, double eps, double rho_backward, double mu_backward,
+                                  double* out, int32_t* active);
+/* dL_dl_box / dL_du_box of QP idx (-1: the whole batch, [B][dim]) as the last pqp_batch_backward_box with n_rhs == 1 left
+ * them; either pointer may be NULL. */
+int pqp_batch_get_backward_box(pqp_batch* h, int64_t idx, double* dL_dl_box, double* dL_du_box);
 /* The backward pass of the closest-feasible QPLayer (reference bindings/python/proxsuite/torch/qplayer.py:371-610) for
  * the QPs first .. first + count - 1, SOLVED with primal_infeasibility_solving and single-sided inequalities (every l at
  * -1e20, as the layer's forward states them).  `loss_derivatives` is [count][dim + 2 n_eq + 2 n_in], host or device

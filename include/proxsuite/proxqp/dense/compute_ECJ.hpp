@@ -4,6 +4,9 @@
 // (include/proxsuite/proxqp/dense/compute_ECJ.hpp:29-132); the work is one launch of
 // pqp_backward_kernel through pqp_batch_backward_range (include/proxqp_hip.h).  compute_backward_multi /
 // solution_jacobians: K loss derivatives of one QP in one launch (pqp_batch_backward_multi).
+// A QP with box constraints (is_box_constrained()) goes through pqp_batch_backward_box: its constraint list is [C; I], a
+// loss derivative has dim + n_eq + n_in + dim entries (dL/dx | dL/dy | dL/dz_in | dL/dz_box), and backward_data also
+// receives dL_dl_box / dL_du_box.
 #ifndef PROXSUITE_AMD_PROXQP_DENSE_COMPUTE_ECJ_HPP
 #define PROXSUITE_AMD_PROXQP_DENSE_COMPUTE_ECJ_HPP
 
@@ -25,6 +28,16 @@ pull_backward(QP<T>& qp)
   bd.initialize(qp.model.dim, qp.model.n_eq, qp.model.n_in);
   check(pqp_batch_get_backward(qp.pool()->h, qp.slot(), bd.dL_dH.data(), bd.dL_dg.data(), bd.dL_dA.data(),
                                bd.dL_db.data(), bd.dL_dC.data(), bd.dL_du.data(), bd.dL_dl.data()));
+  if (qp.is_box_constrained())
+    check(pqp_batch_get_backward_box(qp.pool()->h, qp.slot(), bd.dL_dl_box.data(), bd.dL_du_box.data()));
+}
+
+// entries of a loss derivative / of a row (V_x, V_y, V_z): the inequality part covers [C; I] for a QP with box constraints
+template<typename T>
+inline isize
+backward_width(const QP<T>& qp)
+{
+  return qp.model.dim + qp.model.n_eq + qp.model.n_in + (qp.is_box_constrained() ? qp.model.dim : 0);
 }
 } // namespace detail
 
@@ -32,9 +45,11 @@ template<typename T>
 void
 compute_backward(QP<T>& solved_qp, VecRef<T> loss_derivative, T eps = 1.E-4, T rho_new = 1.E-6, T mu_new = 1.E-6)
 {
-  const isize ntot = solved_qp.model.dim + solved_qp.model.n_eq + solved_qp.model.n_in;
+  const isize ntot = detail::backward_width(solved_qp);
   if (loss_derivative.size() != ntot)
-    detail::bad_size("the loss derivative has dim + n_eq + n_in entries.", loss_derivative.size(), ntot);
+    detail::bad_size(solved_qp.is_box_constrained() ? "the loss derivative has dim + n_eq + n_in + dim entries."
+                                                    : "the loss derivative has dim + n_eq + n_in entries.",
+                     loss_derivative.size(), ntot);
   std::vector<T> tmp;
   const T* p = loss_derivative.ptr;
   if (loss_derivative.stride != 1) {
@@ -45,7 +60,10 @@ compute_backward(QP<T>& solved_qp, VecRef<T> loss_derivative, T eps = 1.E-4, T r
   }
   detail::PoolLock lock(solved_qp.pool()->mtx); // (the pool's handle is shared with the other QPs of the pool)
   solved_qp.push_settings();
-  detail::check(pqp_batch_backward_range(solved_qp.pool()->h, solved_qp.slot(), 1, p, eps, rho_new, mu_new));
+  if (solved_qp.is_box_constrained())
+    detail::check(pqp_batch_backward_box(solved_qp.pool()->h, solved_qp.slot(), 1, 1, p, eps, rho_new, mu_new, nullptr, nullptr));
+  else
+    detail::check(pqp_batch_backward_range(solved_qp.pool()->h, solved_qp.slot(), 1, p, eps, rho_new, mu_new));
   detail::pull_backward(solved_qp);
   solved_qp.pull(); // results.info carries the backward proximal parameters, as in the reference
 }
@@ -54,7 +72,8 @@ compute_backward(QP<T>& solved_qp, VecRef<T> loss_derivative, T eps = 1.E-4, T r
 // ONE launch (pqp_batch_backward_multi): the factorisation at (rho_new, mu_new) is done once, the refined KKT solve per
 // row.  Returns the K x (dim + n_eq + n_in) matrix of rows (V_x, V_y, V_z): dL_dg = V_x, dL_db = -V_y, dL_du / dL_dl =
 // -V_z where the constraint is active from above / below (`active`, optional: n_in flags, bit 0 above, bit 1 below).
-// qp.model.backward_data is left alone.
+// qp.model.backward_data is left alone.  With box constraints: rows of dim + n_eq + n_in + dim entries
+// (V_x, V_y, V_zin, V_zbox) and n_in + dim flags.
 template<typename T>
 Mat<T>
 compute_backward_multi(QP<T>& solved_qp,
@@ -64,19 +83,21 @@ compute_backward_multi(QP<T>& solved_qp,
                        T mu_new = 1.E-6,
                        std::vector<std::int32_t>* active = nullptr)
 {
-  const isize ntot = solved_qp.model.dim + solved_qp.model.n_eq + solved_qp.model.n_in;
+  const bool box = solved_qp.is_box_constrained();
+  const isize ntot = detail::backward_width(solved_qp);
   if (loss_derivatives.cols() != ntot)
-    detail::bad_size("a loss derivative has dim + n_eq + n_in entries.", loss_derivatives.cols(), ntot);
+    detail::bad_size(box ? "a loss derivative has dim + n_eq + n_in + dim entries." : "a loss derivative has dim + n_eq + n_in entries.",
+                     loss_derivatives.cols(), ntot);
   const isize K = loss_derivatives.rows();
   Mat<T> ld(K, ntot), out(K, ntot);
   for (isize k = 0; k < K; ++k)
     for (isize i = 0; i < ntot; ++i)
       ld(k, i) = loss_derivatives(k, i);
-  std::vector<std::int32_t> flags(usize(solved_qp.model.n_in), 0);
+  std::vector<std::int32_t> flags(usize(solved_qp.model.n_in + (box ? solved_qp.model.dim : 0)), 0);
   detail::PoolLock lock(solved_qp.pool()->mtx);
   solved_qp.push_settings();
-  detail::check(pqp_batch_backward_multi(solved_qp.pool()->h, solved_qp.slot(), 1, K, ld.data(), eps, rho_new, mu_new,
-                                         out.data(), flags.data()));
+  detail::check((box ? pqp_batch_backward_box : pqp_batch_backward_multi)(solved_qp.pool()->h, solved_qp.slot(), 1, K, ld.data(), eps,
+                                                                          rho_new, mu_new, out.data(), flags.data()));
   solved_qp.pull(); // results.info carries the backward proximal parameters, as after compute_backward
   if (active)
     *active = flags;
@@ -89,6 +110,7 @@ template<typename T>
 struct SolutionJacobians
 {
   Mat<T> dx_dg, dx_db, dx_du, dx_dl; // dim x dim, dim x n_eq, dim x n_in, dim x n_in
+  Mat<T> dx_dl_box, dx_du_box;       // dim x dim for a QP with box constraints, empty otherwise
 };
 
 template<typename T>
@@ -96,13 +118,22 @@ SolutionJacobians<T>
 solution_jacobians(QP<T>& solved_qp, T eps = 1.E-4, T rho_new = 1.E-6, T mu_new = 1.E-6)
 {
   const isize n = solved_qp.model.dim, ne = solved_qp.model.n_eq, ni = solved_qp.model.n_in;
-  Mat<T> ld(n, n + ne + ni);
+  const bool box = solved_qp.is_box_constrained();
+  Mat<T> ld(n, detail::backward_width(solved_qp));
   for (isize i = 0; i < n; ++i)
     ld(i, i) = T(1);
   std::vector<std::int32_t> active;
   const Mat<T> V = compute_backward_multi(solved_qp, MatRef<T>(ld), eps, rho_new, mu_new, &active);
-  SolutionJacobians<T> J{ Mat<T>(n, n), Mat<T>(n, ne), Mat<T>(n, ni), Mat<T>(n, ni) };
+  SolutionJacobians<T> J{ Mat<T>(n, n), Mat<T>(n, ne), Mat<T>(n, ni), Mat<T>(n, ni), Mat<T>(), Mat<T>() };
+  if (box) {
+    J.dx_dl_box.resize(n, n);
+    J.dx_du_box.resize(n, n);
+  }
   for (isize i = 0; i < n; ++i) {
+    for (isize k = 0; box && k < n; ++k) {
+      J.dx_du_box(i, k) = (active[usize(ni + k)] & 1) ? -V(i, n + ne + ni + k) : T(0);
+      J.dx_dl_box(i, k) = (active[usize(ni + k)] & 2) ? -V(i, n + ne + ni + k) : T(0);
+    }
     for (isize k = 0; k < n; ++k)
       J.dx_dg(i, k) = V(i, k);
     for (isize k = 0; k < ne; ++k)

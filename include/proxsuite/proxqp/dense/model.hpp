@@ -28,8 +28,13 @@ struct BackwardData
   Mat<T> dL_dC;
   Vec<T> dL_du;
   Vec<T> dL_dl;
+  // wrt the bounds of a QP with box constraints (length dim); zero for a QP without
+  Vec<T> dL_dl_box;
+  Vec<T> dL_du_box;
   void initialize(isize dim, isize n_eq, isize n_in)
   {
+    dL_dl_box.resize(dim);
+    dL_du_box.resize(dim);
     dL_dH.resize(dim, dim);
     dL_dg.resize(dim);
     dL_dA.resize(n_eq, dim);

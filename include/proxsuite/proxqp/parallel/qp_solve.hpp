@@ -92,16 +92,21 @@ qp_solve_backward_in_parallel(optional<const usize> /*num_threads*/, BatchQP<T>&
     if (p.used == 0)
       continue;
     detail::PoolLock lock(p.mtx);
-    const usize ntot = usize(p.dim + p.n_eq + p.n_in);
+    const bool box = p.n_c != p.n_in; // (QPs with box constraints: loss derivatives over [C; I], pqp_batch_backward_box)
+    const usize ntot = usize(p.dim + p.n_eq + p.n_c);
     std::vector<T> ld(usize(p.used) * ntot);
     for (usize s = 0; s < e.members.size(); ++s) {
       const Vec<T>& v = loss_derivatives[usize(e.members[s])];
       if (usize(v.size()) != ntot)
-        detail::bad_size("the loss derivative has dim + n_eq + n_in entries.", v.size(), isize(ntot));
+        detail::bad_size(box ? "the loss derivative has dim + n_eq + n_in + dim entries." : "the loss derivative has dim + n_eq + n_in entries.",
+                         v.size(), isize(ntot));
       std::memcpy(ld.data() + s * ntot, v.data(), ntot * sizeof(T));
       qps[e.members[s]].push_settings();
     }
-    detail::check(pqp_batch_backward_range(p.h, 0, p.used, ld.data(), eps, rho_new, mu_new));
+    if (box)
+      detail::check(pqp_batch_backward_box(p.h, 0, p.used, 1, ld.data(), eps, rho_new, mu_new, nullptr, nullptr));
+    else
+      detail::check(pqp_batch_backward_range(p.h, 0, p.used, ld.data(), eps, rho_new, mu_new));
     for (usize s = 0; s < e.members.size(); ++s) {
       detail::pull_backward(qps[e.members[s]]);
       qps[e.members[s]].pull();
@@ -125,7 +130,8 @@ qp_solve_backward_in_parallel(optional<const usize> num_threads, std::vector<QP<
   for (auto& kv : groups) {
     const detail::Pool& p = *kv.first;
     detail::PoolLock lock(p.mtx);
-    const usize ntot = usize(p.dim + p.n_eq + p.n_in);
+    const bool box = p.n_c != p.n_in;
+    const usize ntot = usize(p.dim + p.n_eq + p.n_c);
     std::vector<T> ld(kv.second.size() * ntot);
     std::vector<int64_t> idx;
     idx.reserve(kv.second.size());
@@ -133,12 +139,17 @@ qp_solve_backward_in_parallel(optional<const usize> num_threads, std::vector<QP<
       const usize i = kv.second[k];
       const Vec<T>& v = loss_derivatives[i];
       if (usize(v.size()) != ntot)
-        detail::bad_size("the loss derivative has dim + n_eq + n_in entries.", v.size(), isize(ntot));
+        detail::bad_size(box ? "the loss derivative has dim + n_eq + n_in + dim entries." : "the loss derivative has dim + n_eq + n_in entries.",
+                         v.size(), isize(ntot));
       std::memcpy(ld.data() + k * ntot, v.data(), ntot * sizeof(T));
       qps[i].push_settings();
       idx.push_back(int64_t(qps[i].slot()));
     }
-    detail::check(pqp_batch_backward_subset(p.h, idx.data(), int64_t(idx.size()), ld.data(), eps, rho_new, mu_new));
+    if (box)
+      detail::check(pqp_batch_backward_box_subset(p.h, idx.data(), int64_t(idx.size()), 1, ld.data(), eps, rho_new, mu_new, nullptr,
+                                                  nullptr));
+    else
+      detail::check(pqp_batch_backward_subset(p.h, idx.data(), int64_t(idx.size()), ld.data(), eps, rho_new, mu_new));
     for (usize i : kv.second) {
       detail::pull_backward(qps[i]);
       qps[i].pull();

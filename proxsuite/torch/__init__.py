@@ -2,7 +2,7 @@
 import sys as _sys
 
 from proxsuite_amd.torch import qplayer  # noqa: F401
-from proxsuite_amd.torch.qplayer import QPFunction  # noqa: F401
+from proxsuite_amd.torch.qplayer import QPFunction, QPFunctionBox  # noqa: F401
 
 _sys.modules[__name__ + ".qplayer"] = qplayer
-__all__ = ["QPFunction", "qplayer"]
+__all__ = ["QPFunction", "QPFunctionBox", "qplayer"]

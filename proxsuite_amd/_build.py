@@ -52,7 +52,7 @@ def build_randqp(force: bool = False) -> Path:
 # pqp_kernels.hip is compiled once per kernel family (see its header): every solve kernel is
 # ~350 KB of inlined code and takes about a minute of hipcc time, so the objects are built in
 # parallel and linked into one shared library.
-KERNEL_TUS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22)
+KERNEL_TUS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24)
 # families outside the solver (19: the eigenvalue estimates of pqp_eig.hpp): built and linked like the others, their
 # resources frozen in a record of their own (tests/golden/eig_kernel_resources_expected.json) -- the solver's frozen record
 # names the solver's kernels and no others
@@ -62,7 +62,11 @@ AUXILIARY_TUS = (19,)
 # an HBM slice (tests/golden/backward_multi_kernel_resources_expected.json)
 # 22, the closest-feasible QPLayer's backward pass: the assembly of its linear systems and its jacobians (csrc/pqp_infeas.hpp,
 # tests/golden/infeas_backward_kernel_resources_expected.json)
-NAMED_TUS = {"backward_multi": (20, 21), "infeas_backward": (22,)}
+# 23 / 24, the backward pass of QPs with box constraints, in LDS and on an HBM slice, and the kernel that forms its nine
+# jacobians (tests/golden/bwbox_kernel_resources_expected.json, written by --freeze under the name below)
+NAMED_TUS = {"backward_multi": (20, 21), "infeas_backward": (22,), "backward_box": (23, 24)}
+# (the frozen record of a group is <RECORD_NAMES.get(group, group)>_kernel_resources_expected.json)
+RECORD_NAMES = {"backward_box": "bwbox"}
 OBJ_DIR = ROOT / "build" / "obj"
 
 
@@ -311,7 +315,7 @@ def freeze_kernel_resources():
     (p.parent / "eig_kernel_resources_expected.json").write_text(json.dumps(aux, indent=1, sort_keys=True))
     for name in NAMED_TUS:
         grp = {k: {f: v[f] for f in keep if f in v} for k, v in sorted(kernel_resources(auxiliary=name).items()) if k.startswith("pqp_")}
-        (p.parent / ("%s_kernel_resources_expected.json" % name)).write_text(json.dumps(grp, indent=1, sort_keys=True))
+        (p.parent / ("%s_kernel_resources_expected.json" % RECORD_NAMES.get(name, name))).write_text(json.dumps(grp, indent=1, sort_keys=True))
     return p
 
 

@@ -64,7 +64,8 @@ class NativeLib:
                "pqp_multi_gather_device", "pqp_multi_get_trace", "pqp_multi_last_solve_ms", "pqp_box_calibrate",
                "pqp_batch_host_results_fresh_range", "pqp_batch_init_eig", "pqp_batch_update_eig", "pqp_multi_init_eig",
                "pqp_multi_update_eig", "pqp_estimate_min_eigenvalues", "pqp_batch_backward_multi",
-               "pqp_batch_backward_multi_subset", "pqp_batch_backward_closest_feasible")
+               "pqp_batch_backward_multi_subset", "pqp_batch_backward_closest_feasible", "pqp_batch_backward_box",
+               "pqp_batch_backward_box_subset", "pqp_batch_get_backward_box")
 
     def __init__(self, path, legacy=False):
         """legacy=True (A/B scripts only): an older build of the library that lacks the newer entries can still be
@@ -125,6 +126,10 @@ class NativeLib:
         L.pqp_batch_backward_multi.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, _DP] + [C.c_double] * 3 + [_DP, C.POINTER(C.c_int32)]
         L.pqp_batch_backward_multi_subset.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64, C.c_int64, _DP] + [C.c_double] * 3 + \
             [_DP, C.POINTER(C.c_int32)]
+        L.pqp_batch_backward_box.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, _DP] + [C.c_double] * 3 + [_DP, C.POINTER(C.c_int32)]
+        L.pqp_batch_backward_box_subset.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64, C.c_int64, _DP] + [C.c_double] * 3 + \
+            [_DP, C.POINTER(C.c_int32)]
+        L.pqp_batch_get_backward_box.argtypes = [vp, C.c_int64, _DP, _DP]
         L.pqp_batch_backward_closest_feasible.argtypes = [vp, C.c_int64, C.c_int64, _DP, C.c_double, C.c_double, C.c_int64,
                                                           C.c_int64, _DP, C.POINTER(C.c_int32)]
         L.pqp_multi_create.argtypes = [C.c_int64] * 4 + [C.c_int] * 3 + [C.POINTER(C.c_int), C.c_int, C.POINTER(vp)]
@@ -546,6 +551,81 @@ class Batch:
         else:
             self.lib.check(self.lib.L.pqp_batch_backward_multi(self._h, int(first), rows, *args))
         return V, act
+
+    def backward_box(self, loss_derivatives, eps=1e-4, rho_backward=1e-6, mu_backward=1e-6, first=None, count=None,
+                     idx=None, into=None):
+        """pqp_batch_backward_box(_subset): the backward pass of a handle created with box_constraints, over the
+        constraint list [C; I].  `loss_derivatives`: [rows, K, n + n_eq + n_in + n] = (dL/dx | dL/dy | dL/dz_in |
+        dL/dz_box) (numpy or torch, host or ROCm), rows as for backward_multi.  Returns (V, active) where the input lives:
+        V [rows, K, n + n_eq + n_in + n] = (V_x, V_y, V_zin, V_zbox), active [rows, n_in + n] int32 (bit 0: active from
+        above, bit 1: from below).  With K == 1 the nine jacobians are left for backward_box_results().  `into=(V, active)`
+        fills the caller's buffers of the same kind instead."""
+        nc = self.n_in + self.n
+        ntot = self.n + self.n_eq + nc
+        ii = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
+        if ii is not None:
+            first, rows = 0, len(ii)
+        elif first is None:
+            first, rows = 0, self.B
+        else:
+            rows = int(1 if count is None else count)
+        is_torch = hasattr(loss_derivatives, "data_ptr")
+        if is_torch:
+            import torch
+            ld = loss_derivatives.detach()
+            if ld.dtype != torch.float64 or not ld.is_contiguous():
+                ld = ld.to(torch.float64).contiguous()
+        else:
+            ld = np.ascontiguousarray(np.asarray(loss_derivatives, dtype=np.float64))
+        if len(ld.shape) != 3 or tuple(ld.shape[::2]) != (rows, ntot):
+            raise ValueError("wrong argument size: loss_derivatives has shape %s, expected (%d, K, %d)"
+                             % (tuple(ld.shape), rows, ntot))
+        K = int(ld.shape[1])
+        if into is not None:
+            V, act = into
+        elif is_torch:
+            V = torch.zeros((rows, K, ntot), dtype=torch.float64, device=ld.device)
+            act = torch.zeros((rows, nc), dtype=torch.int32, device=ld.device)
+        else:
+            V, act = np.zeros((rows, K, ntot)), np.zeros((rows, nc), dtype=np.int32)
+        for name, buf, shape in (("V", V, (rows, K, ntot)), ("active", act, (rows, nc))):
+            ok = (buf.is_contiguous() if hasattr(buf, "data_ptr") else buf.flags["C_CONTIGUOUS"]) and tuple(buf.shape) == shape
+            if not ok or hasattr(buf, "data_ptr") != is_torch or (is_torch and buf.device != ld.device):
+                raise ValueError("backward_box: %s must be contiguous, of shape %s and live where loss_derivatives lives"
+                                 % (name, shape))
+        if is_torch and ld.is_cuda:
+            torch.cuda.current_stream(ld.device).synchronize()  # (the entry runs on the handle's stream and is synchronous)
+        ptr = (lambda t: t.data_ptr()) if is_torch else (lambda a: a.ctypes.data)
+        args = (K, C.cast(ptr(ld), _DP), float(eps), float(rho_backward), float(mu_backward), C.cast(ptr(V), _DP),
+                C.cast(ptr(act), C.POINTER(C.c_int32)))
+        if ii is not None:
+            self.lib.check(self.lib.L.pqp_batch_backward_box_subset(self._h, ii.ctypes.data_as(C.POINTER(C.c_int64)), rows, *args))
+        else:
+            self.lib.check(self.lib.L.pqp_batch_backward_box(self._h, int(first), rows, *args))
+        return V, act
+
+    def backward_box_results(self, idx=-1, into=None):
+        """the nine jacobians a backward_box call with K == 1 left: those of backward_results() (dL_dC over the n_in general
+        rows) and dL_dl_box, dL_du_box of length n; a dict of numpy arrays, or filled into the given tensors / arrays"""
+        pre = (self.B,) if idx < 0 else ()
+        shapes = dict(dL_dl_box=pre + (self.n,), dL_du_box=pre + (self.n,))
+        out = self.backward_results(idx, into)
+        ptrs = []
+        for name in ("dL_dl_box", "dL_du_box"):
+            buf = out.get(name)
+            if buf is None and into is None:
+                buf = out[name] = np.zeros(shapes[name])
+            if buf is None:
+                ptrs.append(None)
+            elif hasattr(buf, "data_ptr"):
+                import torch
+                if buf.dtype != torch.float64 or not buf.is_contiguous() or tuple(buf.shape) != shapes[name]:
+                    raise ValueError("backward_box_results: %s must be contiguous float64 of shape %s" % (name, shapes[name]))
+                ptrs.append(C.cast(buf.data_ptr(), _DP))
+            else:
+                ptrs.append(buf.ctypes.data_as(_DP))
+        self.lib.check(self.lib.L.pqp_batch_get_backward_box(self._h, int(idx), *ptrs))
+        return out
 
     def backward_closest_feasible(self, loss_derivatives, eps=1e-4, rho=1e-3, max_iter=10, first=0, count=None,
                                   qps_per_pass=0):

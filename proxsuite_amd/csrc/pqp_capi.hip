@@ -1502,6 +1502,152 @@ pqp_batch_backward_multi_subset(pqp_batch* h, const int64_t* idx, int64_t count,
   return backward_multi_impl(h, 0, count, idx, n_rhs, loss_derivatives, eps, rho_backward, mu_backward, out, active);
 }
 
+// pqp_batch_backward_box / _subset: backward_multi_impl for a box handle, rows and flags over the n_in + n rows of [C; I];
+// n_rhs == 1 also forms the nine jacobians from the row
+static int
+backward_box_impl(pqp_batch* h, int64_t first, int64_t count, const int64_t* idx, int64_t n_rhs,
+                  const double* loss_derivatives, double eps, double rho_backward, double mu_backward, double* out,
+                  int32_t* active)
+{
+  if (!h)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "null batch handle");
+  if (!h->dev.d.box)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "pqp_batch_backward_box is defined for handles created with box_constraints: "
+                                          "pqp_batch_backward, pqp_batch_backward_range / _subset and "
+                                          "pqp_batch_backward_multi / _multi_subset serve this one");
+  std::vector<int> order;
+  if (idx) {
+    if (count < 0 || count > h->dev.B)
+      return fail(PQP_ERR_INVALID_ARGUMENT, "subset larger than the batch");
+    order.resize(size_t(count));
+    std::vector<char> seen(size_t(h->dev.B), 0);
+    for (int64_t i = 0; i < count; ++i) {
+      if (idx[i] < 0 || idx[i] >= h->dev.B)
+        return fail(PQP_ERR_INVALID_ARGUMENT, "QP index out of range");
+      if (seen[size_t(idx[i])])
+        return fail(PQP_ERR_INVALID_ARGUMENT, "pqp_batch_backward_box_subset: a QP index is listed twice");
+      seen[size_t(idx[i])] = 1;
+      order[size_t(i)] = int(idx[i]);
+    }
+  } else if (first < 0 || count < 0 || first + count > h->dev.B)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "backward range outside the batch");
+  if (!loss_derivatives)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "loss_derivatives is required");
+  if (n_rhs < 0)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "n_rhs is negative");
+  const pqp::Dims& d = h->dev.d;
+  const size_t nc = size_t(d.nc), ntot = size_t(d.n) + size_t(d.n_eq) + nc;
+  const size_t lim = std::numeric_limits<int64_t>::max() / sizeof(double);
+  if (count > 0 && n_rhs > 0 && (size_t(n_rhs) > lim / size_t(count) || size_t(count) * size_t(n_rhs) > lim / ntot))
+    return fail(PQP_ERR_INVALID_ARGUMENT, "count * n_rhs * (dim + n_eq + n_in + dim) overflows");
+  if (count == 0 || n_rhs == 0)
+    return PQP_OK;
+  if (int rc = settle(h))
+    return rc;
+  PQP_ON_DEVICE(h->device);
+  if (int rc = backward_ready(h, first, count, idx))
+    return rc;
+  const size_t total = size_t(count) * size_t(n_rhs) * ntot, nflags = size_t(count) * nc;
+  const bool ld_in_place = pqp_device_readable(loss_derivatives), out_in_place = out && pqp_device_readable(out);
+  const bool active_in_place = active && pqp_device_readable(active);
+  const bool jacobians = n_rhs == 1; // (they are formed from the row and the flags: both are kept then, asked for or not)
+  int rc = 0;
+  if (!ld_in_place) {
+    if ((rc = grow(h, &h->bwm_ld, &h->bwm_ld_cap, total)))
+      return rc;
+    HIP_TRY(hipMemcpy(h->bwm_ld, loss_derivatives, total * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (!out_in_place && (rc = grow(h, &h->bwm_out, &h->bwm_out_cap, total)))
+    return rc;
+  if (!active_in_place && (active || jacobians) && (rc = grow(h, &h->bwm_active, &h->bwm_active_cap, nflags)))
+    return rc;
+  if (jacobians) {
+    if ((rc = backward_arrays(h)))
+      return rc;
+    const size_t B = size_t(h->dev.B), n = size_t(d.n);
+    if (!h->bw_dlb && ((rc = dalloc(h, &h->bw_dlb, B * n)) || (rc = dalloc(h, &h->bw_dub, B * n))))
+      return rc;
+  }
+  if ((rc = upload_settings(h)))
+    return rc;
+  pqp::BackwardMultiArgs m{};
+  m.ld = ld_in_place ? loss_derivatives : h->bwm_ld;
+  m.eps = eps;
+  m.rho_new = rho_backward;
+  m.mu_new = mu_backward;
+  m.out = out_in_place ? out : h->bwm_out;
+  m.active = active_in_place ? reinterpret_cast<int*>(active) : ((active || jacobians) ? h->bwm_active : nullptr);
+  m.n_rhs = long(n_rhs);
+  m.first = long(first);
+  m.order = nullptr;
+  if (idx) {
+    HIP_TRY(hipMemcpy(h->d_order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
+    h->order_valid = false;
+    m.order = h->d_order;
+  }
+  for (int64_t i = 0; i < count; ++i)
+    mirror_stale(h, idx ? idx[i] : first + i);
+  if ((rc = h->vec_scratch ? pqp_launch_bwbox_hbm(h, m, long(count)) : pqp_launch_bwbox(h, m, long(count))))
+    return rc;
+  if (jacobians) {
+    pqp::BackwardArgs bw{};
+    bw.dL_dH = h->bw_dH;
+    bw.dL_dg = h->bw_dg;
+    bw.dL_dA = h->bw_dA;
+    bw.dL_db = h->bw_db;
+    bw.dL_dC = h->bw_dC;
+    bw.dL_du = h->bw_du;
+    bw.dL_dl = h->bw_dl;
+    bw.first = m.first;
+    bw.order = m.order;
+    if ((rc = pqp_launch_bwbox_outer(h, bw, h->bw_dlb, h->bw_dub, m.out, m.active, long(count))))
+      return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (out && !out_in_place)
+    HIP_TRY(hipMemcpy(out, h->bwm_out, total * sizeof(double), hipMemcpyDeviceToHost));
+  if (active && !active_in_place && nflags)
+    HIP_TRY(hipMemcpy(active, h->bwm_active, nflags * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return PQP_OK;
+}
+
+int
+pqp_batch_backward_box(pqp_batch* h, int64_t first, int64_t count, int64_t n_rhs, const double* loss_derivatives,
+                       double eps, double rho_backward, double mu_backward, double* out, int32_t* active)
+{
+  return backward_box_impl(h, first, count, nullptr, n_rhs, loss_derivatives, eps, rho_backward, mu_backward, out, active);
+}
+
+int
+pqp_batch_backward_box_subset(pqp_batch* h, const int64_t* idx, int64_t count, int64_t n_rhs,
+                              const double* loss_derivatives, double eps, double rho_backward, double mu_backward,
+                              double* out, int32_t* active)
+{
+  if (!h || (count > 0 && !idx))
+    return fail(PQP_ERR_INVALID_ARGUMENT, "null argument");
+  // (an empty subset has no list to read: it is the empty range)
+  return backward_box_impl(h, 0, count, count > 0 ? idx : nullptr, n_rhs, loss_derivatives, eps, rho_backward, mu_backward, out,
+                           active);
+}
+
+int
+pqp_batch_get_backward_box(pqp_batch* h, int64_t idx, double* dL_dl_box, double* dL_du_box)
+{
+  if (int rc = check_idx(h, idx))
+    return rc;
+  if (!h->bw_dlb)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "pqp_batch_backward_box with n_rhs == 1 has not been called on this batch");
+  if (int rc = settle(h))
+    return rc;
+  PQP_ON_DEVICE(h->device);
+  const size_t n = size_t(h->dev.d.n);
+  const int64_t B = h->dev.B;
+  int rc = 0;
+  if ((rc = copy_out(dL_dl_box, h->bw_dlb, idx, B, n)) || (rc = copy_out(dL_du_box, h->bw_dub, idx, B, n)))
+    return rc;
+  return PQP_OK;
+}
+
 int
 pqp_batch_backward_range(pqp_batch* h, int64_t first, int64_t count, const double* loss_derivatives, double eps,
                          double rho_backward, double mu_backward)

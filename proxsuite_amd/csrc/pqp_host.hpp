@@ -111,6 +111,8 @@ struct pqp_batch
   // QPLayer backward outputs ([B][...], allocated at the first pqp_batch_backward)
   double *bw_dH = nullptr, *bw_dg = nullptr, *bw_dA = nullptr, *bw_db = nullptr, *bw_dC = nullptr,
          *bw_du = nullptr, *bw_dl = nullptr, *bw_ld = nullptr;
+  // ... and the two a box handle adds (pqp_batch_backward_box with n_rhs = 1, served by pqp_batch_get_backward_box): [B][n]
+  double *bw_dlb = nullptr, *bw_dub = nullptr;
   // pqp_batch_backward_multi: staging of host arguments (grow-only; *_cap in elements) and the rows / flags of the
   // n_rhs = 1 launch a vec_scratch handle's pqp_batch_backward is made of
   double *bwm_ld = nullptr, *bwm_out = nullptr;
@@ -197,6 +199,11 @@ int pqp_launch_backward(pqp_batch* h, const pqp::BackwardArgs& bw, long count);
 int pqp_launch_backward_multi(pqp_batch* h, const pqp::BackwardMultiArgs& bw, long count);
 int pqp_launch_backward_multi_hbm(pqp_batch* h, const pqp::BackwardMultiArgs& bw, long count);
 int pqp_launch_backward_outer(pqp_batch* h, const pqp::BackwardArgs& bw, const double* v, const int* active, long count);
+// the backward pass of a box handle (Solver::backward_box; rows and flags over the n_in + n rows of [C; I]): the same three
+int pqp_launch_bwbox(pqp_batch* h, const pqp::BackwardMultiArgs& bw, long count);
+int pqp_launch_bwbox_hbm(pqp_batch* h, const pqp::BackwardMultiArgs& bw, long count);
+int pqp_launch_bwbox_outer(pqp_batch* h, const pqp::BackwardArgs& bw, double* dL_dlb, double* dL_dub, const double* v,
+                           const int* active, long count);
 // the closest-feasible backward (pqp_infeas.hpp): the linear systems of a pass into a.K / a.r, and the seven jacobians of
 // `bw` from the inner solution a.w
 int pqp_launch_infeas_kkt(pqp_batch* h, pqp::InfeasArgs a);

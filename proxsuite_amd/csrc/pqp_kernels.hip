@@ -27,7 +27,7 @@
 //                                     workgroup barrier orders global accesses within a workgroup as it
 //                                     does LDS ones).  Slow per QP -- every vector access is an L1/L2 round
 //                                     trip -- but it removes the size ceiling below 1024 rows.
-#if PQP_TU == 9 || PQP_TU == 21
+#if PQP_TU == 9 || PQP_TU == 21 || PQP_TU == 24
 #define PQP_VECTORS_IN_HBM 1
 #define PQP_LDS __attribute__((address_space(1)))
 #define PQP_GLOBAL __attribute__((address_space(1)))
@@ -38,7 +38,7 @@
 #endif
 // the translation units whose kernels run at 128 VGPRs per lane keep 4 instead of 8 MFMA k-steps of
 // operand loads in flight in the Z / G build (+2 % at C2 and C4, profiles/r02_ab_compiler_flags.txt)
-#if (PQP_TU == 1 || PQP_TU == 4 || PQP_TU == 8 || PQP_TU == 9 || PQP_TU == 21) && !defined(PQP_ZG_DEPTH)
+#if (PQP_TU == 1 || PQP_TU == 4 || PQP_TU == 8 || PQP_TU == 9 || PQP_TU == 21 || PQP_TU == 24) && !defined(PQP_ZG_DEPTH)
 #define PQP_ZG_DEPTH 4
 #endif
 // (the one-wavefront diagonal kernel is not short of scalar registers: its per-QP pointers are ordinary values -- the
@@ -61,6 +61,10 @@
 //  22  pqp_infeas_kkt_kernel<256>     the backward pass of the closest-feasible QPLayer (pqp_infeas.hpp): the linear system of
 //                                     every QP of a pass, written into the model arrays of the inner handle that solves it;
 //                                     and pqp_infeas_grad_kernel<256>, the seven jacobians from the inner solution
+//  23  pqp_bwbox_kernel<.>          the backward pass of QPs WITH box constraints (Solver::backward_box): the constraint list
+//                                     is [C; I], K loss derivatives per QP; and pqp_bwbox_outer_kernel, which forms the nine
+//                                     jacobians (the seven of pqp_batch_get_backward, dL_dl_box, dL_du_box) from one row
+//  24  pqp_bwbox_hbm_kernel<1024>     the same on a slice of the HBM scratch buffer per workgroup (as 9 and 21)
 #if PQP_TU == 0 || PQP_TU == 22
 #define PQP_INFEAS_DEVICE 1 // (pqp_host.hpp includes pqp_infeas.hpp for the launchers' argument record: the kernels' bodies with it here)
 #endif
@@ -468,6 +472,117 @@ int
 pqp_launch_backward_multi_hbm(pqp_batch* h, const pqp::BackwardMultiArgs& bw, long count)
 {
   hipLaunchKernelGGL((pqp_backward_multi_hbm_kernel<1024>), dim3((unsigned)count), dim3(1024), 0, h->stream, h->dev, bw,
+                     h->vec_scratch, (long)((h->lds_solve + 7) / 8));
+  HIP_TRY(hipGetLastError());
+  return PQP_OK;
+}
+#endif
+
+#if PQP_TU_HAS(23)
+template<int NT>
+__global__ __launch_bounds__(NT, 2) void
+pqp_bwbox_kernel(pqp::Batch batch, pqp::BackwardMultiArgs bw)
+{
+  HIP_DYNAMIC_SHARED(double, smem)
+  pqp::backward_box_body<NT>(batch, bw, (long)blockIdx.x, (pqp::lptr)smem);
+}
+
+template<int NT>
+static int
+launch_bwbox(pqp_batch* h, const pqp::BackwardMultiArgs& bw, long count)
+{
+  if (h->lds_solve > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&pqp_bwbox_kernel<NT>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_solve));
+  hipLaunchKernelGGL((pqp_bwbox_kernel<NT>), dim3((unsigned)count), dim3(NT), h->lds_solve, h->stream, h->dev, bw);
+  HIP_TRY(hipGetLastError());
+  return PQP_OK;
+}
+
+int
+pqp_launch_bwbox(pqp_batch* h, const pqp::BackwardMultiArgs& bw, long count)
+{
+  switch (h->nt) {
+    case 256:
+      return launch_bwbox<256>(h, bw, count);
+    case 512:
+      return launch_bwbox<512>(h, bw, count);
+    default:
+      return launch_bwbox<1024>(h, bw, count);
+  }
+}
+
+// The nine jacobians of a box-constrained QP from one row of a backward_box launch with n_rhs = 1, element-wise and shared
+// out as in pqp_backward_outer_kernel.  v: [count][n + n_eq + n_in + n] rows (dx_u, dy_u, dz_in_u, dz_box_u); active:
+// [count][n_in + n] flags; outputs over the whole batch.  dL_dC covers the n_in general rows: the identity block of
+// [C; I] has no parameter; its rows give dL_du_box / dL_dl_box (length n).
+template<int NT>
+__global__ __launch_bounds__(NT) void
+pqp_bwbox_outer_kernel(pqp::Batch batch, pqp::BackwardArgs bw, double* __restrict__ dL_dlb, double* __restrict__ dL_dub,
+                       const double* __restrict__ v, const int* __restrict__ active, int shares)
+{
+  const long n = batch.d.n, ne = batch.d.n_eq, ni = batch.d.n_in, nc = batch.d.nc;
+  const long slot = blockIdx.x / shares, share = blockIdx.x - slot * shares;
+  const long q = bw.order ? (long)bw.order[slot] : bw.first + slot;
+  const double *dxu = v + slot * (n + ne + nc), *dyu = dxu + n, *dzu = dyu + ne;
+  const int* fl = active + slot * nc;
+  const double *xs = batch.x + q * n, *ys = batch.y + q * ne, *zs = batch.z + q * nc;
+  double *oH = bw.dL_dH + q * n * n, *og = bw.dL_dg + q * n, *oA = bw.dL_dA + q * ne * n, *ob = bw.dL_db + q * ne;
+  double *oC = bw.dL_dC + q * ni * n, *ou = bw.dL_du + q * ni, *ol = bw.dL_dl + q * ni;
+  double *oub = dL_dub + q * n, *olb = dL_dlb + q * n;
+  const long t0 = share * NT + threadIdx.x, step = (long)shares * NT;
+  for (long o = t0; o < n * n; o += step) {
+    const long i = o / n, k = o - i * n;
+    oH[o] = 0.5 * (dxu[i] * xs[k] + xs[i] * dxu[k]);
+  }
+  for (long k = t0; k < n; k += step)
+    og[k] = dxu[k];
+  for (long o = t0; o < ne * n; o += step) {
+    const long i = o / n, k = o - i * n;
+    oA[o] = dyu[i] * xs[k] + ys[i] * dxu[k];
+  }
+  for (long k = t0; k < ne; k += step)
+    ob[k] = -dyu[k];
+  for (long o = t0; o < ni * n; o += step) {
+    const long i = o / n, k = o - i * n;
+    oC[o] = dzu[i] * xs[k] + zs[i] * dxu[k];
+  }
+  for (long i = t0; i < ni; i += step) {
+    ou[i] = (fl[i] & 1) ? -dzu[i] : 0.0;
+    ol[i] = (fl[i] & 2) ? -dzu[i] : 0.0;
+  }
+  for (long k = t0; k < nc - ni; k += step) {
+    oub[k] = (fl[ni + k] & 1) ? -dzu[ni + k] : 0.0;
+    olb[k] = (fl[ni + k] & 2) ? -dzu[ni + k] : 0.0;
+  }
+}
+
+int
+pqp_launch_bwbox_outer(pqp_batch* h, const pqp::BackwardArgs& bw, double* dL_dlb, double* dL_dub, const double* v,
+                       const int* active, long count)
+{
+  const long n = h->dev.d.n, rows = std::max<long>(n, std::max<long>(h->dev.d.n_eq, h->dev.d.n_in));
+  const long shares = std::min<long>(64, std::max<long>(1, (rows * n + 255) / 256));
+  hipLaunchKernelGGL((pqp_bwbox_outer_kernel<256>), dim3((unsigned)(count * shares)), dim3(256), 0, h->stream, h->dev, bw,
+                     dL_dlb, dL_dub, v, active, (int)shares);
+  HIP_TRY(hipGetLastError());
+  return PQP_OK;
+}
+#endif
+
+#if PQP_TU == 24 || (PQP_TU == 0 && defined(PQP_EMULATED_MFMA))
+// (as pqp_backward_multi_hbm_kernel: workgroup i works on the i-th slice of the handle's scratch buffer; no dynamic LDS)
+template<int NT>
+__global__ __launch_bounds__(NT, PQP_WPS_1024) void
+pqp_bwbox_hbm_kernel(pqp::Batch batch, pqp::BackwardMultiArgs bw, double* scratch, long stride)
+{
+  pqp::backward_box_body<NT>(batch, bw, (long)blockIdx.x, (pqp::lptr)(scratch + (long)blockIdx.x * stride));
+}
+
+int
+pqp_launch_bwbox_hbm(pqp_batch* h, const pqp::BackwardMultiArgs& bw, long count)
+{
+  hipLaunchKernelGGL((pqp_bwbox_hbm_kernel<1024>), dim3((unsigned)count), dim3(1024), 0, h->stream, h->dev, bw,
                      h->vec_scratch, (long)((h->lds_solve + 7) / 8));
   HIP_TRY(hipGetLastError());
   return PQP_OK;

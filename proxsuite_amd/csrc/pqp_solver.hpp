@@ -5071,7 +5071,153 @@ struct Solver
       Ww.dirty = 1;
     }
   }
+
+  // ---- backward_multi() for a QP with box constraints: the constraint list is [C; I] (n_c = n_in + n rows, z = [z_in; z_box],
+  // the engine's own numbering: ids >= n_in are box rows), and every loop of compute_backward over the inequalities runs over
+  // those n_c rows in that order -- the active sets, the position-indexed repeated scaling of the right-hand side, the
+  // inactive entries of dz at their permuted position.  The scaling vector is [delta_in; delta_box] (ruiz.hpp applies
+  // delta_box to box vectors as it applies delta_in to the others), which is contiguous in P.delta().  A box row is one
+  // scaled column of W for the engine (build_ZG, apply_active_set, kkt_solve_pm, kkt_residual: their has_box() branches);
+  // nothing here forms the identity block.  Row k goes to out[slot][k][:] as (dx_u, dy_u, dz_in_u, dz_box_u); `active` is
+  // [count][n_c].  With identity equilibration the result is that of backward_multi() on the QP stated with the bounds as
+  // rows n_in .. n_in + n - 1 of C.
+  __device__ __forceinline__ void backward_box(const BackwardMultiArgs& bw, long slot_in_launch)
+  {
+    const int n = d.n, ne = d.n_eq, ni = d.n_in, nc = d.nc;
+    const long ntot = (long)n + ne + nc;
+    for (int k = threadIdx.x; k < ST_COUNT; k += NT)
+      L.stat()[k] = 0;
+    {
+      const State& Wr = *P.state();
+      diag_mode = (SPEC == 0) && d.hessian != PQP_HESSIAN_DENSE && d.n_eq == 0 && Wr.c_diag != 0 &&
+                  !(d.n_in > 0 && d.box != 0);
+      ruiz_c = Wr.ruiz_c;
+    }
+    info.load(*P.info());
+    const double c = ruiz_c;
+    vload(L.x(), P.x(), n);
+    vload(L.y(), P.y(), ne);
+    vload(L.z(), P.z(), nc);
+    if (has_box())
+      vload(L.isc(), P.is(), n); // (the engine's box branches read i_scaled from LDS)
+    cgptr dX = P.dlt_x(), dE = P.dlt_eq(), dI = P.dlt_in(); // dI[0 .. n_c): [delta_in; delta_box]
+    for (int k = threadIdx.x; k < n; k += NT)
+      L.dx()[k] = P.x()[k] / dX[k]; // x in the equilibrated space
+    for (int i = threadIdx.x; i < nc; i += NT) {
+      L.aflags()[i] = 0;
+      L.slot_of()[i] = -1;
+    }
+    __syncthreads();
+    // active sets at the solution (compute_ECJ.hpp:48-57) over [C; I]:  C x + z_in - u >= 0,  C x + z_in - l <= 0 ...
+    if (ni > 0) {
+      mv(P.CTs(), ni, n, ni, L.dx(), L.Cdx()); // (never the diagonal structure: that mode has no general row beside a box)
+      cgptr gu = P.u(), gl = P.l();
+      for (int i = threadIdx.x; i < ni; i += NT) {
+        const double ctz = L.Cdx()[i] / dI[i] + L.z()[i];
+        const bool up = (ctz - gu[i]) >= 0., lo = (ctz - gl[i]) <= 0.;
+        L.aflags()[i] = (up ? 1 : 0) | (lo ? 2 : 0) | ((up || lo) ? 4 : 0);
+      }
+    }
+    // ... and  x + z_box - u_box >= 0,  x + z_box - l_box <= 0  (each lane writes flags no other lane reads before the barrier)
+    if (has_box()) {
+      cgptr bu = P.u_box(), bl = P.l_box();
+      for (int k = threadIdx.x; k < n; k += NT) {
+        const double xz = L.x()[k] + L.z()[ni + k];
+        const bool up = (xz - bu[k]) >= 0., lo = (xz - bl[k]) <= 0.;
+        L.aflags()[ni + k] = (up ? 1 : 0) | (lo ? 2 : 0) | ((up || lo) ? 4 : 0);
+      }
+    }
+    __syncthreads();
+    info.rho = bw.rho_new;
+    info.mu_eq = bw.mu_new;
+    info.mu_in = bw.mu_new;
+    // setup_factorization + active_set_change from the empty set (:66-86)
+    factor_primal_block<false>();
+    n_c = 0;
+    n_slots = 0;
+    r = ne;
+    schur_dirty = true;
+    apply_active_set();
+    const int na = n_c;
+    for (long row = 0; row < bw.n_rhs; ++row) {
+      cgptr ld = (cgptr)(bw.ld + (slot_in_launch * bw.n_rhs + row) * ntot);
+      gptr o = (gptr)(bw.out + (slot_in_launch * bw.n_rhs + row) * ntot);
+      // right-hand side (:88-112)
+      for (int k = threadIdx.x; k < n; k += NT)
+        L.rx()[k] = -ld[k] * (dX[k] * c);
+      for (int k = threadIdx.x; k < ne; k += NT)
+        L.rd()[k] = -ld[n + k] * dE[k];
+      double in_any = 0.0;
+      for (int i = threadIdx.x; i < nc; i += NT)
+        in_any = fmax(in_any, fabs(ld[n + ne + i]));
+      in_any = R.max(in_any);
+      for (int i = threadIdx.x; i < nc; i += NT) {
+        const int a = L.slot_of()[i];
+        if (a >= 0) {
+          double v = 0.0;
+          if (in_any != 0.0) {
+            // written at loop iteration i of the reference, then scaled by [delta_in; delta_box][position a]
+            // at iterations i, i+1, ..., n_c-1
+            v = -ld[n + ne + i];
+            const double s = dI[a];
+            for (int t = i; t < nc; ++t)
+              v *= s;
+          }
+          L.rd()[ne + a] = v;
+        }
+      }
+      __syncthreads();
+      (void)iterative_solve(bw.eps);
+      // compute_backward_loss_ESG (:134-189): unpermute dz, unscale; each lane writes what it computed
+      for (int k = threadIdx.x; k < n; k += NT)
+        o[k] = L.dx()[k] * dX[k];
+      for (int k = threadIdx.x; k < ne; k += NT)
+        o[n + k] = L.sd()[k] * dE[k] / c;
+      for (int j = threadIdx.x; j < nc; j += NT) {
+        const int a = L.slot_of()[j];
+        double v;
+        if (a >= 0) {
+          v = L.sd()[ne + a];
+        } else {
+          // permuted position of an inactive constraint after active_set_change from the identity
+          // map: j + #{active i > j}
+          int before = 0;
+          for (int t = 0; t < na; ++t)
+            before += (L.act()[t] < j) ? 1 : 0;
+          v = ld[n + ne + (j + na - before)];
+        }
+        o[n + ne + j] = v * dI[j] / c;
+      }
+      __syncthreads(); // (the next row rewrites the right-hand side and the solution)
+    }
+    {
+      PQP_GLOBAL int* ga = P.act();
+      PQP_GLOBAL int* fl = (PQP_GLOBAL int*)(bw.active ? bw.active + slot_in_launch * nc : nullptr);
+      for (int i = threadIdx.x; i < nc; i += NT) {
+        ga[i] = act_pack(act_cid(ga[i]), L.aflags()[i]);
+        if (fl)
+          fl[i] = L.aflags()[i] & 3;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      info.store(*P.info());
+      State& Ww = *P.state();
+      Ww.factor_valid = 0;
+      Ww.primal_valid = 0; // (the block in HBM was factorised at rho_new)
+      Ww.ls_valid = 0;
+      Ww.dirty = 1;
+    }
+  }
 };
+
+template<int NT>
+__device__ __forceinline__ void
+backward_box_body(const Batch& batch, const BackwardMultiArgs& bw, long slot, lptr lds_base)
+{
+  Solver<NT, 0> S(batch, bw.order ? (long)bw.order[slot] : bw.first + slot, lds_base);
+  S.backward_box(bw, slot);
+}
 
 template<int NT>
 __device__ __forceinline__ void

@@ -110,11 +110,14 @@ class Results:
 
 class BackwardData:
     """`qp.model.backward_data` (reference dense/backward_data.hpp:27-133): the jacobians of the loss
-    wrt the model, filled by compute_backward / solve_backward_in_parallel."""
+    wrt the model, filled by compute_backward / solve_backward_in_parallel.  dL_dl_box / dL_du_box (length dim): the
+    jacobians wrt the bounds of a QP with box constraints; they stay zero for QPs without."""
 
-    __slots__ = ("dL_dH", "dL_dg", "dL_dA", "dL_db", "dL_dC", "dL_du", "dL_dl")
+    __slots__ = ("dL_dH", "dL_dg", "dL_dA", "dL_db", "dL_dC", "dL_du", "dL_dl", "dL_dl_box", "dL_du_box")
 
     def __init__(self, dim, n_eq, n_in):
+        self.dL_dl_box = np.zeros(dim)
+        self.dL_du_box = np.zeros(dim)
         self.dL_dH = np.zeros((dim, dim))
         self.dL_dg = np.zeros(dim)
         self.dL_dA = np.zeros((n_eq, dim))
@@ -547,15 +550,21 @@ class VectorLossDerivatives(list):
 def _store_backward(qp, rows, i):
     bd = qp.model.backward_data
     for name in BackwardData.__slots__:
-        setattr(bd, name, np.array(rows[name][i]))
+        if name in rows:  # (dL_dl_box / dL_du_box come from the box entry only)
+            setattr(bd, name, np.array(rows[name][i]))
 
 
 def compute_backward(qp, loss_derivative, eps=1e-4, rho_backward=1e-6, mu_backward=1e-6):
     """dense::compute_backward (reference dense/compute_ECJ.hpp:29-132; python expose-backward.hpp):
     fills qp.model.backward_data for one solved QP."""
     ld = np.ascontiguousarray(np.asarray(loss_derivative, dtype=np.float64)).reshape(1, -1)
-    qp._pool.batch.backward(ld, eps, rho_backward, mu_backward, first=qp._slot, count=1)
-    out = qp._pool.batch.backward_results(qp._slot)
+    if qp.is_box_constrained():
+        # the constraint list is [C; I]: loss_derivative has n + n_eq + n_in + n entries (pqp_batch_backward_box)
+        qp._pool.batch.backward_box(ld[:, None, :], eps, rho_backward, mu_backward, first=qp._slot, count=1)
+        out = qp._pool.batch.backward_box_results(qp._slot)
+    else:
+        qp._pool.batch.backward(ld, eps, rho_backward, mu_backward, first=qp._slot, count=1)
+        out = qp._pool.batch.backward_results(qp._slot)
     _store_backward(qp, {k: v[None] for k, v in out.items()}, 0)
     qp._pool.touch()
 
@@ -589,6 +598,17 @@ def compute_backward_multi(qp, loss_derivatives, eps=1e-4, rho_backward=1e-6, mu
     if ld.ndim != 2:
         raise ValueError("wrong argument size: loss_derivatives has shape %s, expected [K, n + n_eq + n_in]" % (ld.shape,))
     batch = qp._pool.batch
+    if qp.is_box_constrained():
+        # rows of n + n_eq + n_in + n entries over [C; I]: dL_du / dL_dl keep the n_in general rows, dL_du_box / dL_dl_box
+        # [K, n] take the box rows; `vectors` and `active` cover all n_in + n
+        V, act = batch.backward_box(ld[None], eps, rho_backward, mu_backward, first=qp._slot, count=1)
+        qp._pool.touch()
+        out = _rows_to_jacobians(V[0], act[0][None, :], batch.n, batch.n_eq)
+        ni = batch.n_in
+        out["dL_du_box"], out["dL_dl_box"] = out["dL_du"][:, ni:], out["dL_dl"][:, ni:]
+        out["dL_du"], out["dL_dl"] = out["dL_du"][:, :ni], out["dL_dl"][:, :ni]
+        out["vectors"], out["active"] = V[0], act[0]
+        return out
     V, act = batch.backward_multi(ld[None], eps, rho_backward, mu_backward, first=qp._slot, count=1)
     qp._pool.touch()
     out = _rows_to_jacobians(V[0], act[0][None, :], batch.n, batch.n_eq)
@@ -598,13 +618,17 @@ def compute_backward_multi(qp, loss_derivatives, eps=1e-4, rho_backward=1e-6, mu
 
 def solution_jacobians(qp, eps=1e-4, rho_backward=1e-6, mu_backward=1e-6):
     """The jacobians of the solution x of one solved QP wrt its vectors, in ONE call (K = n loss derivatives [I_n | 0]):
-    dx_dg [n, n], dx_db [n, n_eq], dx_du and dx_dl [n, n_in] -- row i is compute_backward's dL_dg ... for the loss x_i."""
+    dx_dg [n, n], dx_db [n, n_eq], dx_du and dx_dl [n, n_in] -- row i is compute_backward's dL_dg ... for the loss x_i.
+    A QP with box constraints adds dx_dl_box and dx_du_box [n, n]."""
     batch = qp._pool.batch
     n = batch.n
-    ld = np.zeros((n, n + batch.n_eq + batch.n_in))
+    ld = np.zeros((n, n + batch.n_eq + batch.n_in + (n if qp.is_box_constrained() else 0)))
     ld[:, :n] = np.eye(n)
     r = compute_backward_multi(qp, ld, eps, rho_backward, mu_backward)
-    return dict(dx_dg=r["dL_dg"], dx_db=r["dL_db"], dx_du=r["dL_du"], dx_dl=r["dL_dl"])
+    out = dict(dx_dg=r["dL_dg"], dx_db=r["dL_db"], dx_du=r["dL_du"], dx_dl=r["dL_dl"])
+    if qp.is_box_constrained():
+        out["dx_dl_box"], out["dx_du_box"] = r["dL_dl_box"], r["dL_du_box"]
+    return out
 
 
 def solve_backward_in_parallel(num_threads=None, qps=None, loss_derivatives=None, eps=1e-4, rho_backward=1e-6,
@@ -622,6 +646,15 @@ def solve_backward_in_parallel(num_threads=None, qps=None, loss_derivatives=None
     for pool, items in pools.values():
         items.sort(key=lambda t: t[0])
         slots = [t[0] for t in items]
+        if pool.batch.box:
+            # QPs with box constraints: one launch of the box entry over the subset, n_rhs = 1
+            ld = np.ascontiguousarray(np.stack([t[2] for t in items]))[:, None, :]
+            pool.batch.backward_box(ld, eps, rho_backward, mu_backward, idx=slots)
+            rows = pool.batch.backward_box_results(-1)
+            for s, qp, _ in items:
+                _store_backward(qp, rows, s)
+            pool.touch()
+            continue
         if slots == list(range(slots[0], slots[0] + len(slots))):
             ld = np.ascontiguousarray(np.stack([t[2] for t in items]))
             pool.batch.backward(ld, eps, rho_backward, mu_backward, first=slots[0], count=len(slots))

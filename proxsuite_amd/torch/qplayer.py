@@ -51,7 +51,7 @@ def _dense64(t):
     return t.detach().to(torch.float64).contiguous()
 
 
-# Native batch handles are kept per (batch, dim, n_eq, n_in, device) signature: creating one costs
+# Native batch handles are kept per (batch, dim, n_eq, n_in, device, box_constraints) signature: creating one costs
 # ~45 device allocations + memsets (25 ms at 2048 x (100, 50, 100), against 10 ms for the solve).  A
 # forward checks a handle out; it goes back when the autograd context that owns it dies (after the
 # backward, or with the graph), so two layers of one shape in the same graph never share a handle.
@@ -68,8 +68,8 @@ def _checkout(key):
         # rho = rho_backward, mu = mu_backward in results.info, and init(..., rho=...) keeps mu)
         batch.cleanup(-1)
         return batch
-    nbatch, nz, neq, nineq, index = key
-    return _native.Batch(nbatch, nz, neq, nineq, box_constraints=False, hessian_type=int(HessianType.Dense),
+    nbatch, nz, neq, nineq, index, box = key
+    return _native.Batch(nbatch, nz, neq, nineq, box_constraints=box, hessian_type=int(HessianType.Dense),
                          dense_backend=int(DenseBackend.Automatic), device=index)
 
 
@@ -94,13 +94,17 @@ class _Lease:
             pass
 
 
-def _solve_batch(Q, p, A, b, G, l, u, eps, max_iter, infeasible):
-    nbatch, nineq, nz = G.size()
+def _solve_batch(Q, p, A, b, G, l, u, eps, max_iter, infeasible, l_box=None, u_box=None):
+    """`l_box` / `u_box` ([nbatch, nz]): the handle has box constraints (QPFunctionBox); G may then be empty and z is
+    [nbatch, nineq + nz] = [z_in | z_box]"""
+    box = l_box is not None
+    nbatch, nz = p.size()
+    nineq = G.size(1) if G.nelement() > 0 else 0
     neq = A.size(1) if A.nelement() > 0 else 0
-    assert neq > 0 or nineq > 0
+    assert neq > 0 or nineq > 0 or box
     dev = Q.device
     index = dev.index if dev.type == "cuda" and dev.index is not None else 0
-    key = (int(nbatch), int(nz), int(neq), int(nineq), int(index))
+    key = (int(nbatch), int(nz), int(neq), int(nineq), int(index), box)
     batch = _checkout(key)
     lease = _Lease(key, batch)
     rho = 5.0e-5
@@ -119,14 +123,14 @@ def _solve_batch(Q, p, A, b, G, l, u, eps, max_iter, infeasible):
             cur.synchronize()
     batch.init(-1, _dense64(Q), _dense64(p), _dense64(A) if neq else None, _dense64(b) if neq else None,
                _dense64(G) if nineq else None, _dense64(l) if nineq else None, _dense64(u) if nineq else None,
-               rho=rho)
+               _dense64(l_box) if box else None, _dense64(u_box) if box else None, rho=rho)
     batch.solve()
     opts = dict(dtype=torch.float64, device=dev)
     x = torch.empty((nbatch, nz), **opts)
     y = torch.empty((nbatch, neq), **opts)
-    z = torch.empty((nbatch, nineq), **opts)
+    z = torch.empty((nbatch, batch.n_c), **opts)
     se = torch.empty((nbatch, neq), **opts)
-    si = torch.empty((nbatch, nineq), **opts)
+    si = torch.empty((nbatch, batch.n_c), **opts)
     batch.results_into(x, y, z, se, si)
     return lease, x, y, z, se, si
 
@@ -283,3 +287,67 @@ def QPFunction(eps=1e-9, maxIter=1000, eps_backward=1.0e-4, rho_backward=1.0e-6,
             return tuple(shaped(g, bt[i], sh[i]) for i, g in enumerate(grads))
 
     return QPFunctionFn.apply if structural_feasibility else QPFunctionFn_infeas.apply
+
+
+def QPFunctionBox(eps=1e-9, maxIter=1000, eps_backward=1.0e-4, rho_backward=1.0e-6, mu_backward=1.0e-6):
+    """QPFunction for QPs with variable bounds l_box <= x <= u_box: the function takes (Q, p, A, b, G, l, u, l_box, u_box)
+    and returns (x, y, z, z_box).  The bounds are box constraints of the engine (a handle created with box_constraints:
+    one scaled column per bound instead of a dense identity row under G), and the backward is ONE pqp_batch_backward_box
+    call with one loss derivative per QP, whose nine jacobians are copied device-to-device into the gradient tensors.
+    Parameters shared by the batch are expanded as in QPFunction and receive the sum of the per-QP gradients.  G (with l
+    and u) may be empty."""
+
+    class QPFunctionBoxFn(Function):
+        @staticmethod
+        def forward(ctx, Q_, p_, A_, b_, G_, l_, u_, lb_, ub_):
+            nbatch = _extract_nbatch((Q_, 3), (p_, 2), (A_, 3), (b_, 2), (G_, 3), (l_, 2), (u_, 2), (lb_, 2), (ub_, 2))
+            Q, p, G = _expand(Q_, nbatch, 3), _expand(p_, nbatch, 2), _expand(G_, nbatch, 3)
+            u, l = _expand(u_, nbatch, 2), _expand(l_, nbatch, 2)
+            A, b = _expand(A_, nbatch, 3), _expand(b_, nbatch, 2)
+            lb, ub = _expand(lb_, nbatch, 2), _expand(ub_, nbatch, 2)
+            lease, x, y, z, _, _ = _solve_batch(Q, p, A, b, G, l, u, eps, maxIter, infeasible=False, l_box=lb, u_box=ub)
+            ctx.lease = lease  # the handle returns to the cache when this context is collected
+            ctx.batch = lease.batch
+            ctx.dev = Q.device
+            ctx.dtype = Q.dtype
+            ins = (Q_, p_, A_, b_, G_, l_, u_, lb_, ub_)
+            ctx.shapes = tuple(tuple(t_.shape) if t_.numel() else () for t_ in ins)
+            ctx.batched = tuple(t_.ndimension() == d for t_, d in zip(ins, (3, 2, 3, 2, 3, 2, 2, 2, 2)))
+            ni = lease.batch.n_in
+            t = Q.dtype
+            return x.to(t), y.to(t), z[:, :ni].to(t), z[:, ni:].to(t)
+
+        @staticmethod
+        def backward(ctx, dl_dx, dl_dy, dl_dz, dl_dzbox):
+            batch, dev = ctx.batch, ctx.dev
+            B, n, ne, ni = batch.B, batch.n, batch.n_eq, batch.n_in
+            ld = torch.zeros((B, 1, n + ne + ni + n), dtype=torch.float64, device=dev)
+            if dl_dx is not None:
+                ld[:, 0, :n] = dl_dx
+            if dl_dy is not None and ne:
+                ld[:, 0, n:n + ne] = dl_dy
+            if dl_dz is not None and ni:
+                ld[:, 0, n + ne:n + ne + ni] = dl_dz
+            if dl_dzbox is not None:
+                ld[:, 0, n + ne + ni:] = dl_dzbox
+            batch.backward_box(ld, eps_backward, rho_backward, mu_backward)  # (synchronises the caller's stream itself)
+            opts = dict(dtype=torch.float64, device=dev)
+            out = dict(dL_dH=torch.empty((B, n, n), **opts), dL_dg=torch.empty((B, n), **opts),
+                       dL_dA=torch.empty((B, ne, n), **opts), dL_db=torch.empty((B, ne), **opts),
+                       dL_dC=torch.empty((B, ni, n), **opts), dL_du=torch.empty((B, ni), **opts),
+                       dL_dl=torch.empty((B, ni), **opts), dL_dl_box=torch.empty((B, n), **opts),
+                       dL_du_box=torch.empty((B, n), **opts))
+            batch.backward_box_results(-1, into=out)
+            t = ctx.dtype
+
+            def shaped(g, like_batched, shape):
+                if g.numel() == 0 or len(shape) == 0:
+                    return None
+                # parameters shared by the batch receive the sum of the per-QP gradients
+                return (g if like_batched else g.sum(dim=0)).to(t).reshape(shape)
+
+            bt, sh = ctx.batched, ctx.shapes
+            names = ("dL_dH", "dL_dg", "dL_dA", "dL_db", "dL_dC", "dL_dl", "dL_du", "dL_dl_box", "dL_du_box")
+            return tuple(shaped(out[k], bt[i], sh[i]) for i, k in enumerate(names))
+
+    return QPFunctionBoxFn.apply

@@ -76,6 +76,36 @@ int pqp_batch_update(pqp_batch* h, int64_t idx, const double* H, const double* g
                      const double* l_box, const double* u_box, int update_preconditioner,
                      double rho, double mu_eq, double mu_in, double manual_minimal_H_eigenvalue);
 
+/* Batches that share a model (batched MPC: one H, A, C for every QP; a QPLayer whose weights are 2-D): pqp_batch_init /
+ * pqp_batch_update over the QPs [first, first + count).  An array whose bit is set in `shared_mask` holds ONE QP's worth
+ * and is given to every QP of the range -- it crosses the host link once and is written to the per-QP model arrays by a
+ * kernel on the handle's stream; an array whose bit is clear holds `count` QPs' worth, its first element that of QP
+ * `first`.  A null array is absent, as above, and its bit is ignored.  Pointers are host or device memory.  Afterwards
+ * every byte of the handle is what pqp_batch_init / pqp_batch_update with materialised copies would have left, so
+ * every later solve, backward pass and getter is bit-identical.  The call returns when the source arrays may be
+ * overwritten.  count == 0: PQP_OK, nothing is touched; a range outside the batch: PQP_ERR_INVALID_ARGUMENT.  (The
+ * per-QP eigenvalue arrays of the _eig entries have no shared form.) */
+enum
+{
+  PQP_SHARED_H = 1,
+  PQP_SHARED_G = 2,
+  PQP_SHARED_A = 4,
+  PQP_SHARED_B = 8,
+  PQP_SHARED_C = 16,
+  PQP_SHARED_L = 32,
+  PQP_SHARED_U = 64,
+  PQP_SHARED_LBOX = 128,
+  PQP_SHARED_UBOX = 256
+};
+int pqp_batch_init_shared(pqp_batch* h, int64_t first, int64_t count, const double* H, const double* g, const double* A,
+                          const double* b, const double* C, const double* l, const double* u, const double* l_box,
+                          const double* u_box, int shared_mask, int compute_preconditioner, double rho, double mu_eq,
+                          double mu_in, double manual_minimal_H_eigenvalue);
+int pqp_batch_update_shared(pqp_batch* h, int64_t first, int64_t count, const double* H, const double* g, const double* A,
+                            const double* b, const double* C, const double* l, const double* u, const double* l_box,
+                            const double* u_box, int shared_mask, int update_preconditioner, double rho, double mu_eq,
+                            double mu_in, double manual_minimal_H_eigenvalue);
+
 /* pqp_batch_init / pqp_batch_update with ONE manual_minimal_H_eigenvalue PER ADDRESSED QP: a HOST array of B entries for
  * idx == -1, of one entry otherwise.  A NaN entry, or a null pointer, means "absent", as the scalar's NaN does.  Everything
  * else is the scalar entry's behaviour (an update that acts as a first init does not forward the value either). */
@@ -255,6 +285,17 @@ int pqp_batch_backward_closest_feasible(pqp_batch* h, int64_t first, int64_t cou
  * batch, arrays [B][...]); row-major; any pointer may be NULL. */
 int pqp_batch_get_backward(pqp_batch* h, int64_t idx, double* dL_dH, double* dL_dg, double* dL_dA,
                            double* dL_db, double* dL_dC, double* dL_du, double* dL_dl);
+/* The gradients of SHARED parameters: for each non-null output (host or device memory, one QP's worth) the sum over the
+ * QPs [first, first + count) of what pqp_batch_get_backward / pqp_batch_get_backward_box hand out per QP, formed on the
+ * device after pqp_batch_backward*, pqp_batch_backward_box* with n_rhs == 1 or pqp_batch_backward_closest_feasible.  No
+ * atomics; the order is a function of (first, count) alone: the range is cut into chunks of 64 consecutive QPs starting
+ * at `first`, a chunk is added up sequentially in index order starting from its first term, and the chunk partials are
+ * then added sequentially in chunk order -- the same bits on every device, call after call.  The handle's jacobian
+ * arrays are read, nothing else is written.  count == 0: zeros.  PQP_ERR_INVALID_ARGUMENT: a range outside the batch, no
+ * backward pass yet, dL_dl_box / dL_du_box on a handle without box constraints. */
+int pqp_batch_get_backward_sum(pqp_batch* h, int64_t first, int64_t count, double* dL_dH, double* dL_dg, double* dL_dA,
+                               double* dL_db, double* dL_dC, double* dL_du, double* dL_dl, double* dL_dl_box,
+                               double* dL_du_box);
 
 /* Dispatch order of whole-batch solves: 1 (default) = longest-processing-time first, using the
  * device cycle counts of the previous whole-batch solve of this handle; 0 = index order.  QPs are
@@ -391,6 +432,17 @@ int pqp_multi_update_eig(pqp_multi* m, int64_t idx, const double* H, const doubl
                          const double* C, const double* l, const double* u, const double* l_box, const double* u_box,
                          int update_preconditioner, double rho, double mu_eq, double mu_in,
                          const double* manual_minimal_H_eigenvalue);
+/* pqp_batch_init_shared / pqp_batch_update_shared over the shards: the global range [first, first + count) is split
+ * along them, every shard makes the batch call on its part from a host thread of its own, the shared arrays passed as
+ * they are; bit-exact against the single-handle call */
+int pqp_multi_init_shared(pqp_multi* m, int64_t first, int64_t count, const double* H, const double* g, const double* A,
+                          const double* b, const double* C, const double* l, const double* u, const double* l_box,
+                          const double* u_box, int shared_mask, int compute_preconditioner, double rho, double mu_eq,
+                          double mu_in, double manual_minimal_H_eigenvalue);
+int pqp_multi_update_shared(pqp_multi* m, int64_t first, int64_t count, const double* H, const double* g, const double* A,
+                            const double* b, const double* C, const double* l, const double* u, const double* l_box,
+                            const double* u_box, int shared_mask, int update_preconditioner, double rho, double mu_eq,
+                            double mu_in, double manual_minimal_H_eigenvalue);
 int pqp_multi_warm_start(pqp_multi* m, int64_t idx, const double* x, const double* y, const double* z);
 int pqp_multi_cleanup(pqp_multi* m, int64_t idx);
 int pqp_multi_flush(pqp_multi* m);

@@ -653,6 +653,36 @@ solve(optional<MatRef<T>> H, optional<VecRef<T>> g, optional<MatRef<T>> A, optio
   return Qp.results;
 }
 
+// One argument of BatchQP::init_shared / update_shared: absent (nullopt), ONE value shared by every QP (whatever a
+// MatRef / VecRef is made from: Mat / Vec, a std::vector<T> for a vector, an Eigen-like object), or one value per QP (a
+// std::vector of those, in QP order).
+template<typename Ref>
+struct SharedArg
+{
+  std::vector<Ref> values;
+  bool shared = false;
+  SharedArg() = default;
+  SharedArg(std::nullopt_t) {}
+  SharedArg(const Ref& one)
+    : values{ one }
+    , shared(true)
+  {
+  }
+  template<typename X, typename = std::enable_if_t<std::is_constructible<Ref, const X&>::value>>
+  SharedArg(const X& one)
+    : values{ Ref(one) }
+    , shared(true)
+  {
+  }
+  template<typename X, typename = std::enable_if_t<std::is_constructible<Ref, const X&>::value>>
+  SharedArg(const std::vector<X>& per_qp)
+  {
+    for (const X& v : per_qp)
+      values.emplace_back(v);
+  }
+  bool absent() const { return values.empty() || values[0].size() == 0; }
+};
+
 // dense::BatchQP<T> (reference wrapper.hpp:1253-1311).  `batch_size` is the capacity of each
 // device pool (the reference reserves a std::vector of that many QPs); QPs of different sizes
 // get different pools.  References returned by init_qp_in_place stay valid for the life of the
@@ -706,6 +736,44 @@ struct BatchQP
       q.init(m.H, m.g, m.A, m.b, m.C, m.l, m.u, m.l_box, m.u_box, qp.settings.compute_preconditioner);
     else
       q.init(m.H, m.g, m.A, m.b, m.C, m.l, m.u, qp.settings.compute_preconditioner);
+  }
+
+  // Batches that share a model (batched MPC: one H, A, C for every QP; pqp_batch_init_shared).  init_shared creates
+  // `count` QPs in place -- dimensions from the arguments -- and initialises them with ONE library call per pool (per
+  // shard of a multi-device batch): a shared argument crosses the host link once and is given to every QP on the
+  // device, a per-QP argument holds `count` values.  Returns the index of the first new QP: they are
+  // (*this)[first] .. (*this)[first + count - 1].  The overloads mirror QP::init: without and with box constraints.
+  using SharedMat = SharedArg<MatRef<T>>;
+  using SharedVec = SharedArg<VecRef<T>>;
+  isize init_shared(isize count, SharedMat H, SharedVec g, SharedMat A, SharedVec b, SharedMat C, SharedVec l, SharedVec u,
+                    bool compute_preconditioner = true, optional<T> rho = nullopt, optional<T> mu_eq = nullopt,
+                    optional<T> mu_in = nullopt, HessianType hessian = HessianType::Dense,
+                    DenseBackend backend = DenseBackend::Automatic)
+  {
+    return create_shared(count, false, H, g, A, b, C, l, u, SharedVec(), SharedVec(), compute_preconditioner, rho, mu_eq,
+                         mu_in, hessian, backend);
+  }
+  isize init_shared(isize count, SharedMat H, SharedVec g, SharedMat A, SharedVec b, SharedMat C, SharedVec l, SharedVec u,
+                    SharedVec l_box, SharedVec u_box, bool compute_preconditioner = true, optional<T> rho = nullopt,
+                    optional<T> mu_eq = nullopt, optional<T> mu_in = nullopt, HessianType hessian = HessianType::Dense,
+                    DenseBackend backend = DenseBackend::Automatic)
+  {
+    return create_shared(count, true, H, g, A, b, C, l, u, l_box, u_box, compute_preconditioner, rho, mu_eq, mu_in, hessian,
+                         backend);
+  }
+  // QP::update of EVERY QP of the batch (they must have one signature) with one library call per pool; a per-QP
+  // argument holds size() values.  A later update of a single QP keeps working.
+  void update_shared(SharedMat H, SharedVec g, SharedMat A, SharedVec b, SharedMat C, SharedVec l, SharedVec u,
+                     bool update_preconditioner = false, optional<T> rho = nullopt, optional<T> mu_eq = nullopt,
+                     optional<T> mu_in = nullopt)
+  {
+    setup_shared(false, 0, size(), H, g, A, b, C, l, u, SharedVec(), SharedVec(), update_preconditioner, rho, mu_eq, mu_in);
+  }
+  void update_shared(SharedMat H, SharedVec g, SharedMat A, SharedVec b, SharedMat C, SharedVec l, SharedVec u,
+                     SharedVec l_box, SharedVec u_box, bool update_preconditioner = false, optional<T> rho = nullopt,
+                     optional<T> mu_eq = nullopt, optional<T> mu_in = nullopt)
+  {
+    setup_shared(false, 0, size(), H, g, A, b, C, l, u, l_box, u_box, update_preconditioner, rho, mu_eq, mu_in);
   }
 
   // (the QPs of a BatchQP are views of its pools: the container is movable, not copyable)
@@ -767,6 +835,122 @@ private:
     e.members.push_back(isize(qps_.size()));
     qps_.push_back(QP<T>(dim, n_eq, n_in, box, hessian, backend, e.pool, slot, e.pool->multi ? devices_[usize(e.pool->shard)] : device_));
     return qps_.back();
+  }
+
+  isize create_shared(isize count, bool box, const SharedMat& H, const SharedVec& g, const SharedMat& A, const SharedVec& b,
+                      const SharedMat& C, const SharedVec& l, const SharedVec& u, const SharedVec& l_box,
+                      const SharedVec& u_box, bool flag, const optional<T>& rho, const optional<T>& mu_eq,
+                      const optional<T>& mu_in, HessianType hessian, DenseBackend backend)
+  {
+    const isize dim = !H.absent() ? H.values[0].rows() : (!g.absent() ? g.values[0].size() : 0);
+    const isize n_eq = !A.absent() ? A.values[0].rows() : (!b.absent() ? b.values[0].size() : 0);
+    const isize n_in = !C.absent() ? C.values[0].rows() : (!u.absent() ? u.values[0].size() : (!l.absent() ? l.values[0].size() : 0));
+    const isize first = size();
+    for (isize i = 0; i < count; ++i)
+      emplace(dim, n_eq, n_in, box, hessian, backend);
+    setup_shared(true, first, count, H, g, A, b, C, l, u, l_box, u_box, flag, rho, mu_eq, mu_in);
+    return first;
+  }
+
+  // one model argument of a shared call, packed for the C-ABI: `len` values when shared, count * len otherwise
+  struct Packed
+  {
+    std::vector<T> buf;
+    const T* ptr = nullptr;
+    isize len = 0;
+    bool shared = false;
+    const T* at(isize i) const { return !ptr || shared ? ptr : ptr + i * len; }
+  };
+  template<typename Ref, typename Pack>
+  static Packed pack_shared(const SharedArg<Ref>& a, isize count, isize len, Pack&& pack_one)
+  {
+    Packed p;
+    p.len = len;
+    p.shared = a.shared;
+    if (a.absent() || count == 0)
+      return p;
+    if (!a.shared && isize(a.values.size()) != count)
+      detail::bad_size("a per-QP argument of init_shared / update_shared holds one value per QP.", isize(a.values.size()), count);
+    std::vector<T> tmp;
+    for (const Ref& v : a.values) {
+      const T* one = pack_one(v, tmp);
+      if (!one)
+        detail::bad_size("a per-QP argument of init_shared / update_shared holds one value per QP.", 0, len);
+      p.buf.insert(p.buf.end(), one, one + len);
+    }
+    p.ptr = p.buf.data();
+    return p;
+  }
+
+  void setup_shared(bool is_init, isize first, isize count, const SharedMat& H, const SharedVec& g, const SharedMat& A,
+                    const SharedVec& b, const SharedMat& C, const SharedVec& l, const SharedVec& u, const SharedVec& l_box,
+                    const SharedVec& u_box, bool flag, const optional<T>& rho, const optional<T>& mu_eq,
+                    const optional<T>& mu_in)
+  {
+    if (count <= 0)
+      return;
+    const QP<T>& q0 = qps_[usize(first)];
+    const isize n = q0.model.dim, ne = q0.model.n_eq, ni = q0.model.n_in;
+    const bool box = q0.is_box_constrained();
+    for (isize i = 1; i < count; ++i) {
+      const QP<T>& q = qps_[usize(first + i)];
+      if (q.model.dim != n || q.model.n_eq != ne || q.model.n_in != ni || q.is_box_constrained() != box)
+        throw std::invalid_argument("update_shared: the QPs of the batch must have one signature.");
+    }
+    if (!box && (!l_box.absent() || !u_box.absent()))
+      throw std::invalid_argument("wrong model setup: the QP object is designed without box constraints, but is "
+                                  "used with lower or upper box inequalities.");
+    const auto vec = [](isize len, const char* hint) {
+      return [len, hint](const VecRef<T>& v, std::vector<T>& tmp) { return QP<T>::pack_vec(v, len, tmp, hint); };
+    };
+    const auto mat = [](isize rows, isize cols, const char* rh, const char* ch) {
+      return [rows, cols, rh, ch](const MatRef<T>& m, std::vector<T>& tmp) { return QP<T>::pack_mat(m, rows, cols, tmp, rh, ch); };
+    };
+    const Packed pg = pack_shared(g, count, n, vec(n, "the dimension wrt the primal variable x variable for g is not valid."));
+    const Packed pb = pack_shared(b, count, ne, vec(ne, "the dimension wrt equality constrained variables for b is not valid."));
+    const Packed pu = pack_shared(u, count, ni, vec(ni, "the dimension wrt inequality constrained variables for u is not valid."));
+    const Packed pl = pack_shared(l, count, ni, vec(ni, "the dimension wrt inequality constrained variables for l is not valid."));
+    const Packed plb = pack_shared(l_box, count, n, vec(n, "the dimension wrt box inequality constrained variables for l_box is not valid."));
+    const Packed pub = pack_shared(u_box, count, n, vec(n, "the dimension wrt box inequality constrained variables for u_box is not valid."));
+    const Packed pH = pack_shared(H, count, n * n, mat(n, n, "the row dimension for H is not valid.", "the column dimension for H is not valid."));
+    const Packed pA = pack_shared(A, count, ne * n, mat(ne, n, "the row dimension for A is not valid.", "the column dimension for A is not valid."));
+    const Packed pC = pack_shared(C, count, ni * n, mat(ni, n, "the row dimension for C is not valid.", "the column dimension for C is not valid."));
+    const int mask = (pH.shared ? PQP_SHARED_H : 0) | (pg.shared ? PQP_SHARED_G : 0) | (pA.shared ? PQP_SHARED_A : 0) |
+                     (pb.shared ? PQP_SHARED_B : 0) | (pC.shared ? PQP_SHARED_C : 0) | (pl.shared ? PQP_SHARED_L : 0) |
+                     (pu.shared ? PQP_SHARED_U : 0) | (plb.shared ? PQP_SHARED_LBOX : 0) | (pub.shared ? PQP_SHARED_UBOX : 0);
+    auto fn = is_init ? &pqp_batch_init_shared : &pqp_batch_update_shared;
+    // one call per run of consecutive slots of one pool (a shard of a multi-device batch is a pool)
+    for (isize at = 0; at < count;) {
+      QP<T>& head = qps_[usize(first + at)];
+      isize run = 1;
+      while (at + run < count && qps_[usize(first + at + run)].pool_ == head.pool_ &&
+             qps_[usize(first + at + run)].slot_ == head.slot_ + run)
+        ++run;
+      detail::PoolLock lock(head.pool_->mtx);
+      for (isize i = 0; i < run; ++i)
+        qps_[usize(first + at + i)].push_settings();
+      detail::check(fn(head.pool_->h, head.slot_, run, pH.at(at), pg.at(at), pA.at(at), pb.at(at), pC.at(at), pl.at(at),
+                       pu.at(at), plb.at(at), pub.at(at), mask, flag ? 1 : 0, detail::opt_or_nan(rho),
+                       detail::opt_or_nan(mu_eq), detail::opt_or_nan(mu_in), std::numeric_limits<T>::quiet_NaN()));
+      at += run;
+    }
+    const T inf = std::numeric_limits<T>::infinity();
+    for (isize i = 0; i < count; ++i) {
+      QP<T>& q = qps_[usize(first + i)];
+      QP<T>::remember(q.model.H, pH.at(i), -inf, inf);
+      QP<T>::remember(q.model.g, pg.at(i), -inf, inf);
+      QP<T>::remember(q.model.A, pA.at(i), -inf, inf);
+      QP<T>::remember(q.model.b, pb.at(i), -inf, inf);
+      QP<T>::remember(q.model.C, pC.at(i), -inf, inf);
+      // bounds are clamped to +-1e20 (reference helpers.hpp:588-612)
+      QP<T>::remember(q.model.l, pl.at(i), T(-1e20), inf);
+      QP<T>::remember(q.model.u, pu.at(i), -inf, T(1e20));
+      if (box) {
+        QP<T>::remember(q.model.l_box, plb.at(i), T(-1e20), inf);
+        QP<T>::remember(q.model.u_box, pub.at(i), -inf, T(1e20));
+      }
+      q.pull();
+    }
   }
 
   isize capacity_;

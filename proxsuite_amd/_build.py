@@ -52,7 +52,7 @@ def build_randqp(force: bool = False) -> Path:
 # pqp_kernels.hip is compiled once per kernel family (see its header): every solve kernel is
 # ~350 KB of inlined code and takes about a minute of hipcc time, so the objects are built in
 # parallel and linked into one shared library.
-KERNEL_TUS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24)
+KERNEL_TUS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25)
 # families outside the solver (19: the eigenvalue estimates of pqp_eig.hpp): built and linked like the others, their
 # resources frozen in a record of their own (tests/golden/eig_kernel_resources_expected.json) -- the solver's frozen record
 # names the solver's kernels and no others
@@ -64,7 +64,9 @@ AUXILIARY_TUS = (19,)
 # tests/golden/infeas_backward_kernel_resources_expected.json)
 # 23 / 24, the backward pass of QPs with box constraints, in LDS and on an HBM slice, and the kernel that forms its nine
 # jacobians (tests/golden/bwbox_kernel_resources_expected.json, written by --freeze under the name below)
-NAMED_TUS = {"backward_multi": (20, 21), "infeas_backward": (22,), "backward_box": (23, 24)}
+# 25, batches that share a model: the broadcast of one model array to the QPs of a range and the ordered sum of a per-QP
+# array (csrc/pqp_shared.hpp, tests/golden/shared_model_kernel_resources_expected.json)
+NAMED_TUS = {"backward_multi": (20, 21), "infeas_backward": (22,), "backward_box": (23, 24), "shared_model": (25,)}
 # (the frozen record of a group is <RECORD_NAMES.get(group, group)>_kernel_resources_expected.json)
 RECORD_NAMES = {"backward_box": "bwbox"}
 OBJ_DIR = ROOT / "build" / "obj"
@@ -183,7 +185,9 @@ def build_hip(force: bool = False, extra_flags=(), out: Path = None, tus=KERNEL_
     # (pqp_dwave.hpp is parsed by every kernel family; family 17 instantiates its kernel, and family 6 compiles the host
     # side of its dispatch -- pqp_plan_solve reads dwave_signature / dwave_lds_bytes: inline templates, no code elsewhere)
     # (pqp_eig.hpp: family 19 alone includes it; pqp_capi.hip reads its host half)
-    only = {"pqp_dwave.hpp": ("kernels_17.o", "kernels_6.o"), "pqp_eig.hpp": ("kernels_19.o", "capi.o")}
+    # (pqp_shared.hpp: family 25 alone includes it; pqp_capi.hip reads its constants)
+    only = {"pqp_dwave.hpp": ("kernels_17.o", "kernels_6.o"), "pqp_eig.hpp": ("kernels_19.o", "capi.o"),
+            "pqp_shared.hpp": ("kernels_25.o", "capi.o")}
     def deps_of(o):
         return [h for h in common if h.name not in only or o.name in only[h.name]] + [CSRC / HOST_OBJECTS.get(o.name, "pqp_kernels.hip")]
     def compile_object(o):

@@ -65,7 +65,8 @@ class NativeLib:
                "pqp_batch_host_results_fresh_range", "pqp_batch_init_eig", "pqp_batch_update_eig", "pqp_multi_init_eig",
                "pqp_multi_update_eig", "pqp_estimate_min_eigenvalues", "pqp_batch_backward_multi",
                "pqp_batch_backward_multi_subset", "pqp_batch_backward_closest_feasible", "pqp_batch_backward_box",
-               "pqp_batch_backward_box_subset", "pqp_batch_get_backward_box")
+               "pqp_batch_backward_box_subset", "pqp_batch_get_backward_box", "pqp_batch_init_shared",
+               "pqp_batch_update_shared", "pqp_batch_get_backward_sum", "pqp_multi_init_shared", "pqp_multi_update_shared")
 
     def __init__(self, path, legacy=False):
         """legacy=True (A/B scripts only): an older build of the library that lacks the newer entries can still be
@@ -160,6 +161,9 @@ class NativeLib:
         for name in ("pqp_batch_init_eig", "pqp_batch_update_eig", "pqp_multi_init_eig", "pqp_multi_update_eig"):
             getattr(L, name).argtypes = [vp, C.c_int64] + [_DP] * 9 + [C.c_int] + [C.c_double] * 3 + [_DP]
         L.pqp_estimate_min_eigenvalues.argtypes = [C.c_int, C.c_int64, C.c_int64, vp, C.c_int, C.c_double, C.c_int64, vp, vp]
+        for name in ("pqp_batch_init_shared", "pqp_batch_update_shared", "pqp_multi_init_shared", "pqp_multi_update_shared"):
+            getattr(L, name).argtypes = [vp, C.c_int64, C.c_int64] + [_DP] * 9 + [C.c_int, C.c_int] + [C.c_double] * 4
+        L.pqp_batch_get_backward_sum.argtypes = [vp, C.c_int64, C.c_int64] + [_DP] * 9
         self.L = real
 
     def check(self, rc):
@@ -239,6 +243,27 @@ def _as_array(a, shape, name):
 
 def _opt(v):
     return NAN if v is None else float(v)
+
+
+# PQP_SHARED_* (include/proxqp_hip.h): the arrays of an init_shared / update_shared call that hold ONE QP's worth
+SHARED_BITS = dict(H=1, g=2, A=4, b=8, C=16, l=32, u=64, l_box=128, u_box=256)
+
+
+def shared_mask(shared) -> int:
+    """a mask of PQP_SHARED_* bits, or the names of the shared arrays ("H", "g", "A", "b", "C", "l", "u", "l_box",
+    "u_box") -> the mask"""
+    if shared is None:
+        return 0
+    if isinstance(shared, (int, np.integer)):
+        if int(shared) & ~511:
+            raise ValueError("shared: unknown bits in mask %d" % int(shared))
+        return int(shared)
+    mask = 0
+    for name in shared:
+        if name not in SHARED_BITS:
+            raise ValueError("shared: unknown array %r (one of %s)" % (name, ", ".join(SHARED_BITS)))
+        mask |= SHARED_BITS[name]
+    return mask
 
 
 def _per_qp(v):
@@ -373,6 +398,65 @@ class Batch:
                manual_minimal_H_eigenvalue=None):
         self._setup(self.lib.L.pqp_batch_update, idx, H, g, A, b, C, l, u, l_box, u_box,
                     update_preconditioner, rho, mu_eq, mu_in, manual_minimal_H_eigenvalue)
+
+    def _setup_shared(self, fn, first, count, H, g, A, b, Cm, l, u, l_box, u_box, shared, flag, rho, mu_eq, mu_in, min_eig):
+        first, count = int(first), int(count)
+        mask = shared_mask(shared)
+        one, per = self._shapes(0), {k: (count,) + v for k, v in self._shapes(0).items()}
+        keep, ptrs = [], []
+        for name, arr in (("H", H), ("g", g), ("A", A), ("b", b), ("C", Cm), ("l", l), ("u", u),
+                          ("l_box", l_box), ("u_box", u_box)):
+            k, p = _as_array(arr, one[name] if mask & SHARED_BITS[name] else per[name], name)
+            keep.append(k)
+            ptrs.append(p)
+        self.lib.check(fn(self._h, first, count, *ptrs, mask, int(bool(flag)), _opt(rho), _opt(mu_eq), _opt(mu_in),
+                          _opt(min_eig)))
+
+    def init_shared(self, first, count, H=None, g=None, A=None, b=None, C=None, l=None, u=None, l_box=None, u_box=None,
+                    shared=(), compute_preconditioner=True, rho=None, mu_eq=None, mu_in=None,
+                    manual_minimal_H_eigenvalue=None):
+        """pqp_batch_init_shared: init of the QPs first .. first + count - 1 of a batch that shares (part of) its model.
+        The arrays named in `shared` (names, or a mask of PQP_SHARED_* bits) have ONE QP's shape and are given to every
+        QP of the range on the device; the others have a leading dimension `count`.  numpy arrays or ROCm tensors."""
+        self._setup_shared(self.lib.L.pqp_batch_init_shared, first, count, H, g, A, b, C, l, u, l_box, u_box, shared,
+                           compute_preconditioner, rho, mu_eq, mu_in, manual_minimal_H_eigenvalue)
+
+    def update_shared(self, first, count, H=None, g=None, A=None, b=None, C=None, l=None, u=None, l_box=None, u_box=None,
+                      shared=(), update_preconditioner=False, rho=None, mu_eq=None, mu_in=None,
+                      manual_minimal_H_eigenvalue=None):
+        """pqp_batch_update_shared: update of the QPs first .. first + count - 1, arguments as for init_shared"""
+        self._setup_shared(self.lib.L.pqp_batch_update_shared, first, count, H, g, A, b, C, l, u, l_box, u_box, shared,
+                           update_preconditioner, rho, mu_eq, mu_in, manual_minimal_H_eigenvalue)
+
+    def backward_sum(self, first=0, count=None, into=None):
+        """pqp_batch_get_backward_sum: the jacobians of backward_results() / backward_box_results() SUMMED over the QPs
+        first .. first + count - 1 (default: to the end of the batch) on the device, in a fixed order -- the gradients of
+        parameters the QPs share.  A dict of numpy arrays of ONE QP's shapes, or (`into`) filled into the given arrays /
+        tensors, host or ROCm: only the names `into` holds are summed."""
+        n, ne, ni = self.n, self.n_eq, self.n_in
+        count = self.B - int(first) if count is None else int(count)
+        shapes = dict(dL_dH=(n, n), dL_dg=(n,), dL_dA=(ne, n), dL_db=(ne,), dL_dC=(ni, n), dL_du=(ni,), dL_dl=(ni,),
+                      dL_dl_box=(n,), dL_du_box=(n,))
+        if into is None:
+            out = {k: np.zeros(v) for k, v in shapes.items() if self.box or not k.endswith("_box")}
+        else:
+            out = into
+        ptrs = []
+        for name in shapes:
+            buf = out.get(name)
+            if buf is None or (buf.numel() if hasattr(buf, "numel") else buf.size) == 0:
+                ptrs.append(None)
+            elif hasattr(buf, "data_ptr"):
+                import torch
+                if buf.dtype != torch.float64 or not buf.is_contiguous() or tuple(buf.shape) != shapes[name]:
+                    raise ValueError("backward_sum: %s must be contiguous float64 of shape %s" % (name, shapes[name]))
+                ptrs.append(C.cast(buf.data_ptr(), _DP))
+            else:
+                if buf.dtype != np.float64 or not buf.flags.c_contiguous or tuple(buf.shape) != shapes[name]:
+                    raise ValueError("backward_sum: %s must be a C-contiguous float64 array of shape %s" % (name, shapes[name]))
+                ptrs.append(buf.ctypes.data_as(_DP))
+        self.lib.check(self.lib.L.pqp_batch_get_backward_sum(self._h, int(first), count, *ptrs))
+        return out
 
     def warm_start(self, idx=-1, x=None, y=None, z=None):
         pre = (self.B,) if idx < 0 else ()
@@ -847,6 +931,21 @@ class MultiBatch:
                update_preconditioner=False, rho=None, mu_eq=None, mu_in=None, manual_minimal_H_eigenvalue=None):
         self._setup(self.lib.L.pqp_multi_update, idx, H, g, A, b, C, l, u, l_box, u_box, update_preconditioner, rho,
                     mu_eq, mu_in, manual_minimal_H_eigenvalue)
+
+    _setup_shared = Batch._setup_shared
+
+    def init_shared(self, first, count, H=None, g=None, A=None, b=None, C=None, l=None, u=None, l_box=None, u_box=None,
+                    shared=(), compute_preconditioner=True, rho=None, mu_eq=None, mu_in=None,
+                    manual_minimal_H_eigenvalue=None):
+        """pqp_multi_init_shared: Batch.init_shared over the shards (the global range is split along them)"""
+        self._setup_shared(self.lib.L.pqp_multi_init_shared, first, count, H, g, A, b, C, l, u, l_box, u_box, shared,
+                           compute_preconditioner, rho, mu_eq, mu_in, manual_minimal_H_eigenvalue)
+
+    def update_shared(self, first, count, H=None, g=None, A=None, b=None, C=None, l=None, u=None, l_box=None, u_box=None,
+                      shared=(), update_preconditioner=False, rho=None, mu_eq=None, mu_in=None,
+                      manual_minimal_H_eigenvalue=None):
+        self._setup_shared(self.lib.L.pqp_multi_update_shared, first, count, H, g, A, b, C, l, u, l_box, u_box, shared,
+                           update_preconditioner, rho, mu_eq, mu_in, manual_minimal_H_eigenvalue)
 
     def warm_start(self, idx=-1, x=None, y=None, z=None):
         pre = (self.B,) if idx < 0 else ()

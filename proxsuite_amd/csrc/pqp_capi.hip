@@ -16,6 +16,7 @@
 #include "pqp_host.hpp"
 #include "pqp_diag.hpp"
 #include "pqp_eig.hpp"
+#include "pqp_shared.hpp"
 
 namespace {
 
@@ -183,17 +184,49 @@ host_settings_state_machine(pqp_settings& st, bool is_init, int precond_flag, do
   st.default_rho += std::fabs(st.default_H_eigenvalue_estimate);
 }
 
+// copies `count` QPs worth of one model array to the QPs lo .. lo + count - 1
 int
-enqueue_setup(pqp_batch* h, int64_t idx, bool update_call, const double* H, const double* g,
-              const double* A, const double* b, const double* C, const double* l, const double* u,
-              const double* l_box, const double* u_box, int precond_flag, double rho, double mu_eq,
-              double mu_in, double min_eig, const double* min_eig_per_qp = nullptr)
+copy_in_range(double* dst_base, const double* src, int64_t lo, int64_t count, size_t per_qp)
 {
-  if (int rc = check_idx(h, idx))
-    return rc;
+  if (!src || per_qp == 0 || count == 0)
+    return PQP_OK;
+  HIP_TRY(hipMemcpy(dst_base + size_t(lo) * per_qp, src, per_qp * size_t(count) * sizeof(double), hipMemcpyDefault));
+  return PQP_OK;
+}
+
+// `p` is memory of device `device`, which a kernel of the handle may read in place
+bool
+device_resident(const void* p, int device)
+{
+#ifdef PQP_EMULATED_MFMA
+  (void)p, (void)device; // (the emulated device is the host: every shared array takes the staging path there)
+  return false;
+#else
+  hipPointerAttribute_t a{};
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError(); // (an address the runtime does not know: pageable host memory)
+    return false;
+  }
+  return a.type == hipMemoryTypeDevice && a.device == device;
+#endif
+}
+
+// init / update of the QPs lo .. hi - 1.  An array whose bit is set in `shared_mask` (PQP_SHARED_*) holds ONE QP's worth,
+// given to every QP of the range by the broadcast kernel (pqp_shared.hpp); the others hold hi - lo QPs' worth.
+int
+enqueue_setup_range(pqp_batch* h, int64_t lo, int64_t hi, int shared_mask, bool update_call, const double* H, const double* g,
+                    const double* A, const double* b, const double* C, const double* l, const double* u,
+                    const double* l_box, const double* u_box, int precond_flag, double rho, double mu_eq,
+                    double mu_in, double min_eig, const double* min_eig_per_qp)
+{
   if (int rc = settle(h))
     return rc;
-  mirror_stale(h, idx); // (setup resets or rescales the results by the initial guess, helpers.hpp:522-572)
+  // (setup resets or rescales the results by the initial guess, helpers.hpp:522-572)
+  if (lo == 0 && hi == h->dev.B)
+    mirror_stale(h, -1);
+  else
+    for (int64_t q = lo; q < hi; ++q)
+      mirror_stale(h, q);
   const pqp::Dims& d = h->dev.d;
   // wrapper.hpp:367-372, 542-546, 736-741, 846-850
   if (!d.box && (l_box || u_box))
@@ -201,7 +234,6 @@ enqueue_setup(pqp_batch* h, int64_t idx, bool update_call, const double* H, cons
                 "wrong model setup: the QP object is designed without box constraints, but is "
                 "initialized or updated with lower or upper box inequalities.");
   PQP_ON_DEVICE(h->device);
-  const int64_t lo = idx < 0 ? 0 : idx, hi = idx < 0 ? h->dev.B : idx + 1;
   // one queued command per QP: run what is pending before stacking another one
   for (int64_t q = lo; q < hi; ++q)
     if (h->cmd[size_t(q)].op != pqp::CMD_NONE) {
@@ -211,14 +243,52 @@ enqueue_setup(pqp_batch* h, int64_t idx, bool update_call, const double* H, cons
     }
   const size_t n = size_t(d.n), ne = size_t(d.n_eq), ni = size_t(d.n_in);
   pqp::Batch& D = h->dev;
-  int rc = 0;
-  if ((rc = copy_in(D.H, H, idx, D.B, n * n)) || (rc = copy_in(D.g, g, idx, D.B, n)) ||
-      (rc = copy_in(D.A, A, idx, D.B, ne * n)) || (rc = copy_in(D.b, b, idx, D.B, ne)) ||
-      (rc = copy_in(D.C, C, idx, D.B, ni * n)) || (rc = copy_in(D.l, l, idx, D.B, ni)) ||
-      (rc = copy_in(D.u, u, idx, D.B, ni)))
-    return rc;
-  if (d.box && ((rc = copy_in(D.l_box, l_box, idx, D.B, n)) || (rc = copy_in(D.u_box, u_box, idx, D.B, n))))
-    return rc;
+  struct In
+  {
+    double* dst;
+    const double* src;
+    size_t per_qp;
+    int bit;
+  };
+  const In in[9] = { { D.H, H, n * n, PQP_SHARED_H },   { D.g, g, n, PQP_SHARED_G },   { D.A, A, ne * n, PQP_SHARED_A },
+                     { D.b, b, ne, PQP_SHARED_B },      { D.C, C, ni * n, PQP_SHARED_C }, { D.l, l, ni, PQP_SHARED_L },
+                     { D.u, u, ni, PQP_SHARED_U },      { D.l_box, l_box, n, PQP_SHARED_LBOX },
+                     { D.u_box, u_box, n, PQP_SHARED_UBOX } };
+  // the shared arrays that live on the host are staged side by side (the broadcasts run on the handle's stream while
+  // the next blocking copy is made); those on the handle's device are read in place
+  bool staged[9] = {};
+  size_t stage = 0;
+  for (int k = 0; k < 9; ++k)
+    if (in[k].src && in[k].per_qp && (shared_mask & in[k].bit) && !device_resident(in[k].src, h->device)) {
+      staged[k] = true;
+      stage += in[k].per_qp;
+    }
+  if (stage)
+    if (int rc = grow(h, &h->shared_stage, &h->shared_stage_cap, stage))
+      return rc;
+  bool launched = false;
+  stage = 0;
+  for (int k = 0; k < 9; ++k) {
+    const In& a = in[k];
+    if (!a.src || a.per_qp == 0)
+      continue;
+    if (!(shared_mask & a.bit)) {
+      if (int rc = copy_in_range(a.dst, a.src, lo, hi - lo, a.per_qp))
+        return rc;
+      continue;
+    }
+    const double* src = a.src;
+    if (staged[k]) {
+      HIP_TRY(hipMemcpy(h->shared_stage + stage, a.src, a.per_qp * sizeof(double), hipMemcpyDefault));
+      src = h->shared_stage + stage;
+      stage += a.per_qp;
+    }
+    if (int rc = pqp_launch_broadcast(h, src, a.dst, long(a.per_qp), long(lo), long(hi - lo)))
+      return rc;
+    launched = true;
+  }
+  if (launched) // the call returns when the source arrays (and the staging buffer) may be overwritten
+    HIP_TRY(hipStreamSynchronize(h->stream));
   for (int64_t q = lo; q < hi; ++q) {
     pqp_settings& st = h->settings[size_t(q)];
     bool is_init = !update_call || !h->is_initialized[size_t(q)];
@@ -252,6 +322,34 @@ enqueue_setup(pqp_batch* h, int64_t idx, bool update_call, const double* H, cons
   }
   h->cmd_pending = true;
   return PQP_OK;
+}
+
+int
+enqueue_setup(pqp_batch* h, int64_t idx, bool update_call, const double* H, const double* g,
+              const double* A, const double* b, const double* C, const double* l, const double* u,
+              const double* l_box, const double* u_box, int precond_flag, double rho, double mu_eq,
+              double mu_in, double min_eig, const double* min_eig_per_qp = nullptr)
+{
+  if (int rc = check_idx(h, idx))
+    return rc;
+  return enqueue_setup_range(h, idx < 0 ? 0 : idx, idx < 0 ? h->dev.B : idx + 1, 0, update_call, H, g, A, b, C, l, u, l_box,
+                             u_box, precond_flag, rho, mu_eq, mu_in, min_eig, min_eig_per_qp);
+}
+
+int
+enqueue_setup_shared(pqp_batch* h, int64_t first, int64_t count, int shared_mask, bool update_call, const double* H,
+                     const double* g, const double* A, const double* b, const double* C, const double* l, const double* u,
+                     const double* l_box, const double* u_box, int precond_flag, double rho, double mu_eq, double mu_in,
+                     double min_eig)
+{
+  if (!h)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "null batch handle");
+  if (first < 0 || count < 0 || first > h->dev.B || count > h->dev.B - first)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "QP range outside the batch");
+  if (count == 0)
+    return PQP_OK;
+  return enqueue_setup_range(h, first, first + count, shared_mask, update_call, H, g, A, b, C, l, u, l_box, u_box,
+                             precond_flag, rho, mu_eq, mu_in, min_eig, nullptr);
 }
 
 } // namespace
@@ -537,6 +635,30 @@ pqp_batch_update(pqp_batch* h, int64_t idx, const double* H, const double* g, co
 {
   return enqueue_setup(h, idx, true, H, g, A, b, C, l, u, l_box, u_box, update_preconditioner ? 1 : 0,
                        rho, mu_eq, mu_in, manual_minimal_H_eigenvalue);
+}
+
+int
+pqp_batch_init_shared(pqp_batch* h, int64_t first, int64_t count, const double* H, const double* g, const double* A,
+                      const double* b, const double* C, const double* l, const double* u, const double* l_box,
+                      const double* u_box, int shared_mask, int compute_preconditioner, double rho, double mu_eq,
+                      double mu_in, double manual_minimal_H_eigenvalue)
+{
+  if (h && h->dev.d.box == 0 && (l_box || u_box))
+    return fail(PQP_ERR_INVALID_ARGUMENT,
+                "wrong model setup: the QP object is designed without box constraints, but is "
+                "initialized with lower or upper box inequalities."); // wrapper.hpp:542-546
+  return enqueue_setup_shared(h, first, count, shared_mask, false, H, g, A, b, C, l, u, l_box, u_box,
+                              compute_preconditioner ? 1 : 0, rho, mu_eq, mu_in, manual_minimal_H_eigenvalue);
+}
+
+int
+pqp_batch_update_shared(pqp_batch* h, int64_t first, int64_t count, const double* H, const double* g, const double* A,
+                        const double* b, const double* C, const double* l, const double* u, const double* l_box,
+                        const double* u_box, int shared_mask, int update_preconditioner, double rho, double mu_eq,
+                        double mu_in, double manual_minimal_H_eigenvalue)
+{
+  return enqueue_setup_shared(h, first, count, shared_mask, true, H, g, A, b, C, l, u, l_box, u_box,
+                              update_preconditioner ? 1 : 0, rho, mu_eq, mu_in, manual_minimal_H_eigenvalue);
 }
 
 int
@@ -1821,6 +1943,70 @@ pqp_batch_get_backward(pqp_batch* h, int64_t idx, double* dL_dH, double* dL_dg, 
       (rc = copy_out(dL_dC, h->bw_dC, idx, B, ni * n)) || (rc = copy_out(dL_du, h->bw_du, idx, B, ni)) ||
       (rc = copy_out(dL_dl, h->bw_dl, idx, B, ni)))
     return rc;
+  return PQP_OK;
+}
+
+// The sums over the QPs first .. first + count - 1 of what pqp_batch_get_backward / pqp_batch_get_backward_box hand out per
+// QP, in the order of pqp_shared.hpp: every sum is formed in a buffer of the handle and copied to its (host or device)
+// destination on the handle's stream.
+int
+pqp_batch_get_backward_sum(pqp_batch* h, int64_t first, int64_t count, double* dL_dH, double* dL_dg, double* dL_dA,
+                           double* dL_db, double* dL_dC, double* dL_du, double* dL_dl, double* dL_dl_box,
+                           double* dL_du_box)
+{
+  if (!h)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "null batch handle");
+  if (first < 0 || count < 0 || first > h->dev.B || count > h->dev.B - first)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "QP range outside the batch");
+  const pqp::Dims& d = h->dev.d;
+  if (!d.box && (dL_dl_box || dL_du_box))
+    return fail(PQP_ERR_INVALID_ARGUMENT, "the batch has no box constraints: there is no dL_dl_box / dL_du_box to sum");
+  if (!h->bw_dH)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "pqp_batch_backward has not been called on this batch");
+  if ((dL_dl_box || dL_du_box) && !h->bw_dlb)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "pqp_batch_backward_box with n_rhs == 1 has not been called on this batch");
+  if (int rc = settle(h))
+    return rc;
+  PQP_ON_DEVICE(h->device);
+  const size_t n = size_t(d.n), ne = size_t(d.n_eq), ni = size_t(d.n_in);
+  struct Out
+  {
+    double* dst;
+    const double* src;
+    size_t len;
+  };
+  const Out out[9] = { { dL_dH, h->bw_dH, n * n }, { dL_dg, h->bw_dg, n },  { dL_dA, h->bw_dA, ne * n },
+                       { dL_db, h->bw_db, ne },    { dL_dC, h->bw_dC, ni * n }, { dL_du, h->bw_du, ni },
+                       { dL_dl, h->bw_dl, ni },    { dL_dl_box, h->bw_dlb, n }, { dL_du_box, h->bw_dub, n } };
+  // [the sums, side by side][the chunk partials of the array being summed]
+  const size_t chunks = (size_t(count) + pqp::PQP_SUM_CHUNK - 1) / pqp::PQP_SUM_CHUNK;
+  size_t total = 0, widest = 0;
+  for (const Out& o : out)
+    if (o.dst) {
+      total += o.len;
+      widest = std::max(widest, o.len);
+    }
+  if (total == 0)
+    return PQP_OK;
+  if (int rc = grow(h, &h->sum_partial, &h->sum_partial_cap, total + (chunks > 1 ? chunks * widest : 0)))
+    return rc;
+  double *res = h->sum_partial, *partial = h->sum_partial + total;
+  for (const Out& o : out) {
+    if (!o.dst || o.len == 0)
+      continue;
+    int rc = 0;
+    if (count == 0)
+      HIP_TRY(hipMemsetAsync(res, 0, o.len * sizeof(double), h->stream));
+    else if (chunks == 1)
+      rc = pqp_launch_sum(h, o.src, res, long(o.len), long(first), long(count), pqp::PQP_SUM_CHUNK);
+    else if (!(rc = pqp_launch_sum(h, o.src, partial, long(o.len), long(first), long(count), pqp::PQP_SUM_CHUNK)))
+      rc = pqp_launch_sum(h, partial, res, long(o.len), 0, long(chunks), long(chunks));
+    if (rc)
+      return rc;
+    HIP_TRY(hipMemcpyAsync(o.dst, res, o.len * sizeof(double), hipMemcpyDefault, h->stream));
+    res += o.len;
+  }
+  HIP_TRY(hipStreamSynchronize(h->stream));
   return PQP_OK;
 }
 

@@ -125,6 +125,11 @@ struct pqp_batch
   double *inf_ld = nullptr, *inf_p2c = nullptr;
   int *inf_flags = nullptr, *inf_finite_l = nullptr;
   size_t inf_ld_cap = 0, inf_p2c_cap = 0, inf_flags_cap = 0;
+  // batches that share a model (pqp_shared.hpp; grow-only, *_cap in elements): the staging buffer a shared HOST array of
+  // pqp_batch_init_shared / pqp_batch_update_shared is copied into before it is broadcast, and the chunk partials and the
+  // result of pqp_batch_get_backward_sum (sized on first use)
+  double *shared_stage = nullptr, *sum_partial = nullptr;
+  size_t shared_stage_cap = 0, sum_partial_cap = 0;
   // Longest-processing-time-first dispatch (OFF by default, pqp_batch_set_schedule): after a
   // whole-batch solve the per-QP device cycle counts order the NEXT whole-batch solve of the same
   // handle, most expensive QP first.  QPs are independent, so the order changes nothing but the
@@ -208,6 +213,10 @@ int pqp_launch_bwbox_outer(pqp_batch* h, const pqp::BackwardArgs& bw, double* dL
 // `bw` from the inner solution a.w
 int pqp_launch_infeas_kkt(pqp_batch* h, pqp::InfeasArgs a);
 int pqp_launch_infeas_grad(pqp_batch* h, pqp::InfeasArgs a, const pqp::BackwardArgs& bw);
+// batches that share a model (pqp_shared.hpp): one array of `len` doubles to every QP of a range of a per-QP array, and
+// the sums of a per-QP array over the chunks of `chunk` QPs of a range (out: [chunks][len]); src, dst, out on the device
+int pqp_launch_broadcast(pqp_batch* h, const double* src, double* dst, long len, long first, long count);
+int pqp_launch_sum(pqp_batch* h, const double* src, double* out, long len, long first, long count, long chunk);
 int pqp_launch_order(pqp_batch* h, long count);
 int pqp_launch_pack(pqp_batch* h, long first, long count, double* out, hipStream_t stream);
 

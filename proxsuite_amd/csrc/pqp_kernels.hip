@@ -65,6 +65,9 @@
 //                                     is [C; I], K loss derivatives per QP; and pqp_bwbox_outer_kernel, which forms the nine
 //                                     jacobians (the seven of pqp_batch_get_backward, dL_dl_box, dL_du_box) from one row
 //  24  pqp_bwbox_hbm_kernel<1024>     the same on a slice of the HBM scratch buffer per workgroup (as 9 and 21)
+//  25  pqp_broadcast_kernel<256>     batches that share a model (pqp_shared.hpp): one model array written to every QP of a range
+//                                     (pqp_batch_init_shared / pqp_batch_update_shared), and pqp_sum_kernel<256>, the sum of a
+//                                     per-QP array over a range in a fixed order (pqp_batch_get_backward_sum)
 #if PQP_TU == 0 || PQP_TU == 22
 #define PQP_INFEAS_DEVICE 1 // (pqp_host.hpp includes pqp_infeas.hpp for the launchers' argument record: the kernels' bodies with it here)
 #endif
@@ -73,6 +76,11 @@
 #if PQP_TU == 0 || PQP_TU == 19
 #define PQP_EIG_DEVICE 1
 #include "pqp_eig.hpp"
+#endif
+
+#if PQP_TU == 0 || PQP_TU == 25
+#define PQP_SHARED_DEVICE 1
+#include "pqp_shared.hpp"
 #endif
 
 #define PQP_TU_HAS(k) (PQP_TU == 0 || PQP_TU == (k))
@@ -622,6 +630,53 @@ pqp_launch_infeas_grad(pqp_batch* h, pqp::InfeasArgs a, const pqp::BackwardArgs&
   const long n = h->dev.d.n, rows = std::max<long>(n, std::max<long>(h->dev.d.n_eq, h->dev.d.n_in));
   a.shares = (int)std::min<long>(64, std::max<long>(1, (rows * n + 255) / 256));
   hipLaunchKernelGGL((pqp_infeas_grad_kernel<256>), dim3((unsigned)(a.count * a.shares)), dim3(256), 0, h->stream, h->dev, a, bw);
+  HIP_TRY(hipGetLastError());
+  return PQP_OK;
+}
+#endif
+
+#if PQP_TU_HAS(25)
+template<int NT>
+__global__ __launch_bounds__(NT) void
+pqp_broadcast_kernel(const double* __restrict__ src, double* __restrict__ dst, long len, long first, long count, long tiles,
+                     int pairs)
+{
+  pqp::broadcast_body<NT>(src, dst, len, first, count, tiles, pairs != 0);
+}
+
+template<int NT>
+__global__ __launch_bounds__(NT) void
+pqp_sum_kernel(const double* __restrict__ src, double* __restrict__ out, long len, long first, long count, long chunk,
+               long tiles)
+{
+  pqp::sum_body<NT>(src, out, len, first, count, chunk, tiles);
+}
+
+// src (device memory, `len` doubles) -> dst + q * len for q in [first, first + count), on the handle's stream
+int
+pqp_launch_broadcast(pqp_batch* h, const double* src, double* dst, long len, long first, long count)
+{
+  if (len <= 0 || count <= 0)
+    return PQP_OK;
+  const int pairs = len % 2 == 0;
+  const long per_tile = pairs ? 2 * 256 : 256;
+  const long tiles = (len + per_tile - 1) / per_tile, chunks = (count + pqp::BCAST_QPS - 1) / pqp::BCAST_QPS;
+  hipLaunchKernelGGL((pqp_broadcast_kernel<256>), dim3((unsigned)(tiles * chunks)), dim3(256), 0, h->stream, src, dst, len,
+                     first, count, tiles, pairs);
+  HIP_TRY(hipGetLastError());
+  return PQP_OK;
+}
+
+// out[c * len + e] = sum of src[q * len + e] over the c-th chunk of `chunk` QPs of [first, first + count), sequentially in
+// index order, on the handle's stream
+int
+pqp_launch_sum(pqp_batch* h, const double* src, double* out, long len, long first, long count, long chunk)
+{
+  if (len <= 0 || count <= 0)
+    return PQP_OK;
+  const long tiles = (len + 255) / 256, chunks = (count + chunk - 1) / chunk;
+  hipLaunchKernelGGL((pqp_sum_kernel<256>), dim3((unsigned)(tiles * chunks)), dim3(256), 0, h->stream, src, out, len, first,
+                     count, chunk, tiles);
   HIP_TRY(hipGetLastError());
   return PQP_OK;
 }

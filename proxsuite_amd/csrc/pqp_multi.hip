@@ -133,6 +133,37 @@ multi_setup(pqp_multi* m, Fn fn, int64_t idx, const double* H, const double* g, 
   });
 }
 
+// Fn: pqp_batch_init_shared / pqp_batch_update_shared.  Shard s takes the part of [first, first + count) it holds: a
+// shared array as it is, a per-QP array from the entry of its first QP of the range.
+template<class Fn>
+int
+multi_setup_shared(pqp_multi* m, Fn fn, int64_t first, int64_t count, const double* H, const double* g, const double* A,
+                   const double* b, const double* C, const double* l, const double* u, const double* l_box,
+                   const double* u_box, int mask, int flag, double rho, double mu_eq, double mu_in, double min_eig)
+{
+  if (!m)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "null multi-device handle");
+  if (first < 0 || count < 0 || first > m->B || count > m->B - first)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "QP range outside the batch");
+  if (count == 0)
+    return PQP_OK;
+  const size_t n = size_t(m->d.n), ne = size_t(m->d.n_eq), ni = size_t(m->d.n_in);
+  const auto part = [&](const double* p, int bit, int64_t skip, size_t per_qp) { return (mask & bit) ? p : off(p, skip, per_qp); };
+  return for_shards(m, [&](size_t s) {
+    const int64_t lo = std::max(first, m->first[s]), hi = std::min(first + count, m->first[s] + m->count[s]);
+    if (lo >= hi)
+      return int(PQP_OK);
+    const int64_t k = lo - first; // entries of a per-QP array in front of this shard's part
+    return fn(m->shard[s], lo - m->first[s], hi - lo, part(H, PQP_SHARED_H, k, n * n), part(g, PQP_SHARED_G, k, n),
+              part(A, PQP_SHARED_A, k, ne * n), part(b, PQP_SHARED_B, k, ne), part(C, PQP_SHARED_C, k, ni * n),
+              part(l, PQP_SHARED_L, k, ni), part(u, PQP_SHARED_U, k, ni), part(l_box, PQP_SHARED_LBOX, k, n),
+              part(u_box, PQP_SHARED_UBOX, k, n), mask, flag, rho, mu_eq, mu_in, min_eig);
+  });
+}
+
+} // namespace
+
+extern "C" {
 } // namespace
 
 extern "C" {
@@ -276,6 +307,26 @@ pqp_multi_update(pqp_multi* m, int64_t idx, const double* H, const double* g, co
 {
   return multi_setup(m, pqp_batch_update, idx, H, g, A, b, C, l, u, l_box, u_box, update_preconditioner, rho, mu_eq, mu_in,
                      manual_minimal_H_eigenvalue);
+}
+
+int
+pqp_multi_init_shared(pqp_multi* m, int64_t first, int64_t count, const double* H, const double* g, const double* A,
+                      const double* b, const double* C, const double* l, const double* u, const double* l_box,
+                      const double* u_box, int shared_mask, int compute_preconditioner, double rho, double mu_eq,
+                      double mu_in, double manual_minimal_H_eigenvalue)
+{
+  return multi_setup_shared(m, pqp_batch_init_shared, first, count, H, g, A, b, C, l, u, l_box, u_box, shared_mask,
+                            compute_preconditioner, rho, mu_eq, mu_in, manual_minimal_H_eigenvalue);
+}
+
+int
+pqp_multi_update_shared(pqp_multi* m, int64_t first, int64_t count, const double* H, const double* g, const double* A,
+                        const double* b, const double* C, const double* l, const double* u, const double* l_box,
+                        const double* u_box, int shared_mask, int update_preconditioner, double rho, double mu_eq,
+                        double mu_in, double manual_minimal_H_eigenvalue)
+{
+  return multi_setup_shared(m, pqp_batch_update_shared, first, count, H, g, A, b, C, l, u, l_box, u_box, shared_mask,
+                            update_preconditioner, rho, mu_eq, mu_in, manual_minimal_H_eigenvalue);
 }
 
 int

@@ -435,6 +435,80 @@ class BatchQP:
                  compute_preconditioner=qp.settings.compute_preconditioner, **extra)
         return new
 
+    # -- batches that share a model (pqp_batch_init_shared / pqp_batch_update_shared)
+    _MATRICES = ("H", "A", "C")
+
+    def _shared_call(self, qps, arrays, update, flag, rho, mu_eq, mu_in):
+        """one library call per pool for the QPs `qps` (runs of consecutive slots of one pool): an array of `arrays` with
+        ONE QP's shape is shared, one with a leading dimension len(qps) is per QP, in the order of `qps`"""
+        count = len(qps)
+        shared = [k for k, a in arrays.items() if a is not None and a.ndim == (2 if k in self._MATRICES else 1)]
+        for k, a in arrays.items():
+            if a is not None and k not in shared and (a.ndim != (3 if k in self._MATRICES else 2) or a.shape[0] != count):
+                raise ValueError("wrong argument size: %s has shape %s, expected one QP's shape or a leading dimension %d"
+                                 % (k, a.shape, count))
+        # what qp.model remembers: the ONE array of a shared argument (bounds clamped as QP._remember does), a row of a
+        # per-QP one
+        def kept(k, a):
+            if k in ("l", "l_box"):
+                a = np.maximum(a, -_INF_BOUND)
+            elif k in ("u", "u_box"):
+                a = np.minimum(a, _INF_BOUND)
+            return np.array(a, dtype=np.float64)
+        remembered = {k: kept(k, arrays[k]) for k in shared}
+        at = 0
+        while at < count:
+            pool, slot = qps[at]._pool, qps[at]._slot
+            run = 1
+            while at + run < count and qps[at + run]._pool is pool and qps[at + run]._slot == slot + run:
+                run += 1
+            part = {k: (a if a is None or k in shared else a[at:at + run]) for k, a in arrays.items()}
+            fn = pool.batch.update_shared if update else pool.batch.init_shared
+            fn(slot, run, shared=shared, rho=rho, mu_eq=mu_eq, mu_in=mu_in,
+               **{"update_preconditioner" if update else "compute_preconditioner": flag}, **part)
+            pool.touch()
+            at += run
+        for i, qp in enumerate(qps):
+            for k, a in arrays.items():
+                if a is None:
+                    continue
+                if k in shared:
+                    if remembered[k].shape == getattr(qp.model, k).shape:
+                        setattr(qp.model, k, remembered[k])
+                else:
+                    qp._remember(**{k: a[i]})
+
+    def init_shared(self, count, H=None, g=None, A=None, b=None, C=None, l=None, u=None, l_box=None, u_box=None,
+                    compute_preconditioner=True, rho=None, mu_eq=None, mu_in=None, hessian_type=HessianType.Dense,
+                    dense_backend=DenseBackend.Automatic):
+        """`count` QPs that share (part of) their model -- batched MPC: one H, A, C, per-QP g, b, l, u -- created in place
+        (dimensions from the shapes) and initialised with ONE library call per pool.  An argument with one QP's shape is
+        shared: it crosses the host link once and is given to every QP on the device; an argument with a leading
+        dimension `count` is per QP.  Returns the list of QPs; their `model` members refer to the one shared array."""
+        count = int(count)
+        arrays = dict(H=_host(H), g=_host(g), A=_host(A), b=_host(b), C=_host(C), l=_host(l), u=_host(u),
+                      l_box=_host(l_box), u_box=_host(u_box))
+        dim = next((a.shape[-1] for a in (arrays["H"], arrays["g"], arrays["A"], arrays["C"]) if a is not None), 0)
+        rows = lambda m, v: m.shape[-2] if m is not None else (v.shape[-1] if v is not None else 0)
+        n_eq, n_in = rows(arrays["A"], arrays["b"]), rows(arrays["C"], arrays["u"] if arrays["u"] is not None else arrays["l"])
+        box = arrays["l_box"] is not None or arrays["u_box"] is not None
+        qps = [self.init_qp_in_place(dim, n_eq, n_in, box, hessian_type, dense_backend) for _ in range(count)]
+        self._shared_call(qps, arrays, False, bool(compute_preconditioner), rho, mu_eq, mu_in)
+        return qps
+
+    def update_shared(self, H=None, g=None, A=None, b=None, C=None, l=None, u=None, l_box=None, u_box=None,
+                      update_preconditioner=False, rho=None, mu_eq=None, mu_in=None, qps=None):
+        """QP::update of every QP of `qps` (default: all QPs of the batch; they must have one signature) with ONE library
+        call per pool; shared and per-QP arguments as for init_shared, per-QP rows in the order of `qps`.  A later
+        qp.update(...) on a single QP keeps working and replaces that QP's model entry."""
+        qps = list(self._qps if qps is None else qps)
+        if qps and any((q.model.dim, q.model.n_eq, q.model.n_in, q._box) !=
+                       (qps[0].model.dim, qps[0].model.n_eq, qps[0].model.n_in, qps[0]._box) for q in qps):
+            raise ValueError("update_shared: the QPs must have one signature (dim, n_eq, n_in, box_constraints)")
+        arrays = dict(H=_host(H), g=_host(g), A=_host(A), b=_host(b), C=_host(C), l=_host(l), u=_host(u),
+                      l_box=_host(l_box), u_box=_host(u_box))
+        self._shared_call(qps, arrays, True, bool(update_preconditioner), rho, mu_eq, mu_in)
+
     def get(self, i) -> QP:
         return self._qps[i]
 

@@ -13,6 +13,10 @@ The backward pass (reference qplayer.py:172-253) is ONE pqp_batch_backward launc
 form of dense/compute_ECJ.hpp's compute_backward for every QP of the batch) whose seven jacobians
 are copied device-to-device into the gradient tensors.
 
+Parameters WITHOUT a batch dimension (2-D Q, A, G; 1-D vectors: a layer's weights) are shared by the batch and stay as
+they are: they go through ONE pqp_batch_init_shared, which gives them to every QP on the device, and their gradients are the
+per-QP jacobians summed on the device (pqp_batch_get_backward_sum, csrc/pqp_shared.hpp); no [B, ...] tensor is made for them.
+
 The closest-feasible variant (`structural_feasibility=False`) differentiates through its sparse backend in the
 reference (qplayer.py:371-610): per QP a rectangular linear system K w = r, solved as a QP with zero Hessian, K as
 equality constraints and primal_infeasibility_solving.  That QP is dense and of the kind this engine solves, so here the
@@ -94,13 +98,16 @@ class _Lease:
             pass
 
 
-def _solve_batch(Q, p, A, b, G, l, u, eps, max_iter, infeasible, l_box=None, u_box=None):
-    """`l_box` / `u_box` ([nbatch, nz]): the handle has box constraints (QPFunctionBox); G may then be empty and z is
-    [nbatch, nineq + nz] = [z_in | z_box]"""
+def _solve_batch(Q, p, A, b, G, l, u, eps, max_iter, infeasible, l_box=None, u_box=None, nbatch=None):
+    """The parameters as the caller holds them: a matrix with 2 dimensions / a vector with 1 is SHARED by the `nbatch` QPs
+    and goes through Batch.init_shared as it is -- one copy of it reaches the handle and is given to every QP on the
+    device (csrc/pqp_shared.hpp); nothing of nbatch times its size is materialised.  `nbatch` None: every parameter
+    carries the batch dimension (pqp_batch_init).  `l_box` / `u_box` ([nbatch, nz] or [nz]): the handle has box
+    constraints (QPFunctionBox); G may then be empty and z is [nbatch, nineq + nz] = [z_in | z_box]"""
     box = l_box is not None
-    nbatch, nz = p.size()
-    nineq = G.size(1) if G.nelement() > 0 else 0
-    neq = A.size(1) if A.nelement() > 0 else 0
+    nbatch, nz = p.size(0) if nbatch is None else nbatch, p.size(-1)
+    nineq = G.size(-2) if G.nelement() > 0 else 0
+    neq = A.size(-2) if A.nelement() > 0 else 0
     assert neq > 0 or nineq > 0 or box
     dev = Q.device
     index = dev.index if dev.type == "cuda" and dev.index is not None else 0
@@ -121,9 +128,14 @@ def _solve_batch(Q, p, A, b, G, l, u, eps, max_iter, infeasible, l_box=None, u_b
         batch.set_stream(cur.cuda_stream)
         if cur != torch.cuda.default_stream(dev):
             cur.synchronize()
-    batch.init(-1, _dense64(Q), _dense64(p), _dense64(A) if neq else None, _dense64(b) if neq else None,
-               _dense64(G) if nineq else None, _dense64(l) if nineq else None, _dense64(u) if nineq else None,
-               _dense64(l_box) if box else None, _dense64(u_box) if box else None, rho=rho)
+    model = dict(H=_dense64(Q), g=_dense64(p), A=_dense64(A) if neq else None, b=_dense64(b) if neq else None,
+                 C=_dense64(G) if nineq else None, l=_dense64(l) if nineq else None, u=_dense64(u) if nineq else None,
+                 l_box=_dense64(l_box) if box else None, u_box=_dense64(u_box) if box else None)
+    shared = [k for k, t in model.items() if t is not None and t.ndimension() == (2 if k in ("H", "A", "C") else 1)]
+    if shared:
+        batch.init_shared(0, nbatch, shared=shared, rho=rho, **model)
+    else:
+        batch.init(-1, rho=rho, **model)
     batch.solve()
     opts = dict(dtype=torch.float64, device=dev)
     x = torch.empty((nbatch, nz), **opts)
@@ -133,6 +145,24 @@ def _solve_batch(Q, p, A, b, G, l, u, eps, max_iter, infeasible, l_box=None, u_b
     si = torch.empty((nbatch, batch.n_c), **opts)
     batch.results_into(x, y, z, se, si)
     return lease, x, y, z, se, si
+
+
+def _gradients(batch, names, batched, shapes, dev, dtype, box=False):
+    """The gradient of every parameter of a layer from the jacobians the backward launch left in the handle.  names[i]:
+    the jacobian of parameter i; batched[i]: it carries the batch dimension and receives the per-QP jacobians
+    (Batch.backward_results); a parameter shared by the batch receives their SUM, formed on the device
+    (Batch.backward_sum): no [B, ...] tensor is allocated or fetched for it.  shapes[i] == (): the parameter is absent."""
+    B, n, ne, ni = batch.B, batch.n, batch.n_eq, batch.n_in
+    one = dict(dL_dH=(n, n), dL_dg=(n,), dL_dA=(ne, n), dL_db=(ne,), dL_dC=(ni, n), dL_du=(ni,), dL_dl=(ni,),
+               dL_dl_box=(n,), dL_du_box=(n,))
+    opts = dict(dtype=torch.float64, device=dev)
+    per = {k: torch.empty((B,) + one[k], **opts) for i, k in enumerate(names) if len(shapes[i]) and batched[i]}
+    tot = {k: torch.empty(one[k], **opts) for i, k in enumerate(names) if len(shapes[i]) and not batched[i]}
+    if per:
+        (batch.backward_box_results if box else batch.backward_results)(-1, into=per)
+    if tot:
+        batch.backward_sum(0, B, into=tot)
+    return per, tot
 
 
 def solution_jacobians(Q, p, A, b, G, l, u, eps=1e-9, maxIter=1000, eps_backward=1.0e-4, rho_backward=1.0e-6,
@@ -167,18 +197,16 @@ def QPFunction(eps=1e-9, maxIter=1000, eps_backward=1.0e-4, rho_backward=1.0e-6,
         @staticmethod
         def forward(ctx, Q_, p_, A_, b_, G_, l_, u_):
             nbatch = _extract_nbatch((Q_, 3), (p_, 2), (A_, 3), (b_, 2), (G_, 3), (l_, 2), (u_, 2))
-            Q, p, G = _expand(Q_, nbatch, 3), _expand(p_, nbatch, 2), _expand(G_, nbatch, 3)
-            u, l = _expand(u_, nbatch, 2), _expand(l_, nbatch, 2)
-            A, b = _expand(A_, nbatch, 3), _expand(b_, nbatch, 2)
-            lease, x, y, z, _, _ = _solve_batch(Q, p, A, b, G, l, u, eps, maxIter, infeasible=False)
+            # (parameters shared by the batch stay as they are: _solve_batch hands them to init_shared)
+            lease, x, y, z, _, _ = _solve_batch(Q_, p_, A_, b_, G_, l_, u_, eps, maxIter, infeasible=False, nbatch=nbatch)
             ctx.lease = lease  # the handle returns to the cache when this context is collected
             ctx.batch = lease.batch
-            ctx.dev = Q.device
-            ctx.dtype = Q.dtype
+            ctx.dev = Q_.device
+            ctx.dtype = Q_.dtype
             ctx.shapes = tuple(tuple(t_.shape) if t_.numel() else () for t_ in (Q_, p_, A_, b_, G_, l_, u_))
             ctx.batched = (Q_.ndimension() == 3, p_.ndimension() == 2, A_.ndimension() == 3, b_.ndimension() == 2,
                            G_.ndimension() == 3, l_.ndimension() == 2, u_.ndimension() == 2)
-            return x.to(Q.dtype), y.to(Q.dtype), z.to(Q.dtype)
+            return x.to(Q_.dtype), y.to(Q_.dtype), z.to(Q_.dtype)
 
         @staticmethod
         def backward(ctx, dl_dzhat, dl_dlams, dl_dnus):
@@ -193,37 +221,29 @@ def QPFunction(eps=1e-9, maxIter=1000, eps_backward=1.0e-4, rho_backward=1.0e-6,
             if dev.type == "cuda":
                 torch.cuda.current_stream(dev).synchronize()
             batch.backward(ld, eps_backward, rho_backward, mu_backward)
-            opts = dict(dtype=torch.float64, device=dev)
-            out = dict(dL_dH=torch.empty((B, n, n), **opts), dL_dg=torch.empty((B, n), **opts),
-                       dL_dA=torch.empty((B, ne, n), **opts), dL_db=torch.empty((B, ne), **opts),
-                       dL_dC=torch.empty((B, ni, n), **opts), dL_du=torch.empty((B, ni), **opts),
-                       dL_dl=torch.empty((B, ni), **opts))
-            batch.backward_results(-1, into=out)
-            t = ctx.dtype
-
-            def shaped(g, like_batched, shape):
-                if g.numel() == 0 or len(shape) == 0:
-                    return None
-                # parameters shared by the batch receive the sum of the per-QP gradients
-                return (g if like_batched else g.sum(dim=0)).to(t).reshape(shape)
-
-            bt, sh = ctx.batched, ctx.shapes
+            bt, sh, t = ctx.batched, ctx.shapes, ctx.dtype
             names = ("dL_dH", "dL_dg", "dL_dA", "dL_db", "dL_dC", "dL_dl", "dL_du")
-            return tuple(shaped(out[k], bt[i], sh[i]) for i, k in enumerate(names))
+            # parameters shared by the batch receive the sum of the per-QP gradients
+            per, tot = _gradients(batch, names, bt, sh, dev, t)
+            return tuple((per[k] if bt[i] else tot[k]).to(t).reshape(sh[i]) if len(sh[i]) else None
+                         for i, k in enumerate(names))
 
     class QPFunctionFn_infeas(Function):
         @staticmethod
         def forward(ctx, Q_, p_, A_, b_, G_, l_, u_):
             n_in, nz = G_.size()[-2:]
             nbatch = _extract_nbatch((Q_, 3), (p_, 2), (A_, 3), (b_, 2), (G_, 3), (l_, 2), (u_, 2))
-            Q, p, G = _expand(Q_, nbatch, 3), _expand(p_, nbatch, 2), _expand(G_, nbatch, 3)
-            u, l = _expand(u_, nbatch, 2), _expand(l_, nbatch, 2)
-            A, b = _expand(A_, nbatch, 3), _expand(b_, nbatch, 2)
-            # single-sided restatement, as the reference does (qplayer.py:270-271)
-            h = torch.cat((-l, u), dim=1)
-            G1 = torch.cat((-G, G), dim=1)
-            lo = torch.full_like(h, -1.0e20)
-            lease, x, y, z, se, si = _solve_batch(Q, p, A, b, G1, lo, h, eps, maxIter, infeasible=True)
+            # single-sided restatement, as the reference does (qplayer.py:270-271), of the parameters as they are: G1 of
+            # a shared G is shared; h is shared when both l and u are (else the shared one of the two vectors is expanded)
+            if l_.ndimension() != u_.ndimension():
+                l, u = _expand(l_, nbatch, 2), _expand(u_, nbatch, 2)
+            else:
+                l, u = l_, u_
+            h = torch.cat((-l, u), dim=-1)
+            G1 = torch.cat((-G_, G_), dim=-2)
+            lo = torch.full((2 * int(n_in),), -1.0e20, dtype=h.dtype, device=h.device)  # (the same for every QP)
+            lease, x, y, z, se, si = _solve_batch(Q_, p_, A_, b_, G1, lo, h, eps, maxIter, infeasible=True, nbatch=nbatch)
+            Q = Q_
             ctx.lease = lease
             ctx.batch = lease.batch  # (its result arrays are the inputs of the backward)
             ctx.n_in = int(n_in)
@@ -266,25 +286,23 @@ def QPFunction(eps=1e-9, maxIter=1000, eps_backward=1.0e-4, rho_backward=1.0e-6,
             if dl_ds_i is not None and ni:
                 halves(n + 2 * ne + ni, dl_ds_i)
             batch.backward_closest_feasible(ld, eps_backward)
-            opts = dict(dtype=torch.float64, device=dev)
-            out = dict(dL_dH=torch.empty((B, n, n), **opts), dL_dg=torch.empty((B, n), **opts),
-                       dL_dA=torch.empty((B, ne, n), **opts), dL_db=torch.empty((B, ne), **opts),
-                       dL_dC=torch.empty((B, ni, n), **opts), dL_du=torch.empty((B, ni), **opts))
-            batch.backward_results(-1, into=out)
+            bt, sh, t = ctx.batched, ctx.shapes, ctx.dtype
+            # the jacobians of the single-sided QP: l and u both come from dL_du of h = [-l; u], per QP for the batched
+            # one of the two and summed for the shared one.  dL_dC is fetched per QP even for a shared G: its two halves
+            # are the jacobians of -G and G, which cancel in the fold below (1e8 against 1e2 at eps_backward = 1e-9), so
+            # the fold has to come BEFORE the sum
+            names = ("dL_dH", "dL_dg", "dL_dA", "dL_db", "dL_dC", "dL_du", "dL_du")
+            fetch = tuple(b or i == 4 for i, b in enumerate(bt))
+            per, tot = _gradients(batch, names, fetch, sh, dev, t)
+            pick = lambda i: per[names[i]] if fetch[i] else tot[names[i]]
             # back to the double-sided parameters: G1 = [-G; G], h = [-l; u]
-            dC, du1 = out["dL_dC"], out["dL_du"]
-            grads = (out["dL_dH"], out["dL_dg"], out["dL_dA"], out["dL_db"], dC[:, ns:] - dC[:, :ns], -du1[:, :ns],
-                     du1[:, ns:])
-            t = ctx.dtype
-
-            def shaped(g, like_batched, shape):
-                if g.numel() == 0 or len(shape) == 0:
-                    return None
-                # parameters shared by the batch receive the sum of the per-QP gradients
-                return (g if like_batched else g.sum(dim=0)).to(t).reshape(shape)
-
-            bt, sh = ctx.batched, ctx.shapes
-            return tuple(shaped(g, bt[i], sh[i]) for i, g in enumerate(grads))
+            fold = (lambda g: g, lambda g: g, lambda g: g, lambda g: g, lambda g: g[:, ns:] - g[:, :ns],
+                    lambda g: -g[..., :ns], lambda g: g[..., ns:])
+            # parameters shared by the batch receive the sum of the per-QP gradients
+            grads = [fold[i](pick(i)) if len(sh[i]) else None for i in range(7)]
+            if grads[4] is not None and not bt[4]:
+                grads[4] = grads[4].sum(dim=0)
+            return tuple(g.to(t).reshape(sh[i]) if g is not None else None for i, g in enumerate(grads))
 
     return QPFunctionFn.apply if structural_feasibility else QPFunctionFn_infeas.apply
 
@@ -294,18 +312,16 @@ def QPFunctionBox(eps=1e-9, maxIter=1000, eps_backward=1.0e-4, rho_backward=1.0e
     and returns (x, y, z, z_box).  The bounds are box constraints of the engine (a handle created with box_constraints:
     one scaled column per bound instead of a dense identity row under G), and the backward is ONE pqp_batch_backward_box
     call with one loss derivative per QP, whose nine jacobians are copied device-to-device into the gradient tensors.
-    Parameters shared by the batch are expanded as in QPFunction and receive the sum of the per-QP gradients.  G (with l
+    Parameters shared by the batch are handled as in QPFunction and receive the sum of the per-QP gradients.  G (with l
     and u) may be empty."""
 
     class QPFunctionBoxFn(Function):
         @staticmethod
         def forward(ctx, Q_, p_, A_, b_, G_, l_, u_, lb_, ub_):
             nbatch = _extract_nbatch((Q_, 3), (p_, 2), (A_, 3), (b_, 2), (G_, 3), (l_, 2), (u_, 2), (lb_, 2), (ub_, 2))
-            Q, p, G = _expand(Q_, nbatch, 3), _expand(p_, nbatch, 2), _expand(G_, nbatch, 3)
-            u, l = _expand(u_, nbatch, 2), _expand(l_, nbatch, 2)
-            A, b = _expand(A_, nbatch, 3), _expand(b_, nbatch, 2)
-            lb, ub = _expand(lb_, nbatch, 2), _expand(ub_, nbatch, 2)
-            lease, x, y, z, _, _ = _solve_batch(Q, p, A, b, G, l, u, eps, maxIter, infeasible=False, l_box=lb, u_box=ub)
+            lease, x, y, z, _, _ = _solve_batch(Q_, p_, A_, b_, G_, l_, u_, eps, maxIter, infeasible=False, l_box=lb_,
+                                                u_box=ub_, nbatch=nbatch)
+            Q = Q_
             ctx.lease = lease  # the handle returns to the cache when this context is collected
             ctx.batch = lease.batch
             ctx.dev = Q.device
@@ -331,23 +347,11 @@ def QPFunctionBox(eps=1e-9, maxIter=1000, eps_backward=1.0e-4, rho_backward=1.0e
             if dl_dzbox is not None:
                 ld[:, 0, n + ne + ni:] = dl_dzbox
             batch.backward_box(ld, eps_backward, rho_backward, mu_backward)  # (synchronises the caller's stream itself)
-            opts = dict(dtype=torch.float64, device=dev)
-            out = dict(dL_dH=torch.empty((B, n, n), **opts), dL_dg=torch.empty((B, n), **opts),
-                       dL_dA=torch.empty((B, ne, n), **opts), dL_db=torch.empty((B, ne), **opts),
-                       dL_dC=torch.empty((B, ni, n), **opts), dL_du=torch.empty((B, ni), **opts),
-                       dL_dl=torch.empty((B, ni), **opts), dL_dl_box=torch.empty((B, n), **opts),
-                       dL_du_box=torch.empty((B, n), **opts))
-            batch.backward_box_results(-1, into=out)
-            t = ctx.dtype
-
-            def shaped(g, like_batched, shape):
-                if g.numel() == 0 or len(shape) == 0:
-                    return None
-                # parameters shared by the batch receive the sum of the per-QP gradients
-                return (g if like_batched else g.sum(dim=0)).to(t).reshape(shape)
-
-            bt, sh = ctx.batched, ctx.shapes
+            bt, sh, t = ctx.batched, ctx.shapes, ctx.dtype
             names = ("dL_dH", "dL_dg", "dL_dA", "dL_db", "dL_dC", "dL_dl", "dL_du", "dL_dl_box", "dL_du_box")
-            return tuple(shaped(out[k], bt[i], sh[i]) for i, k in enumerate(names))
+            # parameters shared by the batch receive the sum of the per-QP gradients
+            per, tot = _gradients(batch, names, bt, sh, dev, t, box=True)
+            return tuple((per[k] if bt[i] else tot[k]).to(t).reshape(sh[i]) if len(sh[i]) else None
+                         for i, k in enumerate(names))
 
     return QPFunctionBoxFn.apply

@@ -238,6 +238,31 @@ int pqp_batch_backward_multi(pqp_batch* h, int64_t first, int64_t count, int64_t
 int pqp_batch_backward_multi_subset(pqp_batch* h, const int64_t* idx, int64_t count, int64_t n_rhs,
                                     const double* loss_derivatives, double eps, double rho_backward, double mu_backward,
                                     double* out, int32_t* active);
+/* Forward-mode sensitivities (tangents, JVP) of the solved QPs first .. first + count - 1: by how much (x, y, z) move when
+ * the parameters move by (dH, dg, dA, db, dC, dl, du), for n_dir directions per QP on ONE factorisation -- the adjoint of
+ * pqp_batch_backward_multi.  With the flags of that entry (bit 0: C x + z - u >= 0, bit 1: C x + z - l <= 0) a direction has
+ *   r_x = (dH + dH^T) x / 2 + dg + dA^T y + dC^T z,   r_y = dA x - db,   r_z[i] = (dC x)[i] - [bit 0] du[i] - [bit 1] dl[i]
+ * and its tangent T = (T_x, T_y, T_z) solves the system pqp_batch_backward factorises (regularised with (rho, mu, mu),
+ * restricted to the active rows, in the equilibrated space) with right-hand side -r; inactive rows of T_z are 0.  Then
+ * <ld, T> = sum over the parameters of <dL/dtheta, dtheta> for the jacobians pqp_batch_backward returns for ld.  A row with
+ * both flags set takes du and dl (it needs C x + z = l = u exactly).
+ * Tangent arrays are [count][n_dir][...] row-major with the shapes of one QP's model arrays; a bit PQP_SHARED_H ..
+ * PQP_SHARED_U of `shared_mask` says ONE [n_dir][...] block serves every QP of the range.  A NULL array is a zero tangent
+ * and is not read; all NULL is valid and yields zeros.  `out` is [count][n_dir][dim + n_eq + n_in], `active` (may be NULL)
+ * [count][n_in], `rhs` (may be NULL) receives (r_x | r_y | dC x) per QP and direction, [count][n_dir][dim + n_eq + n_in].
+ * Pointers are host or device memory (host arrays are staged through buffers of the handle).  Synchronous, on the handle's
+ * stream.  Errors, no-ops and the QPs' state afterwards are those of pqp_batch_backward_multi: a dual infeasible QP, a
+ * range outside the batch, a NULL `out`, n_dir < 0 or a size that overflows: PQP_ERR_INVALID_ARGUMENT; n_dir == 0 or
+ * count == 0: PQP_OK, nothing is touched.  A handle with box constraints: PQP_ERR_UNSUPPORTED (no box tangents). */
+int pqp_batch_tangent_multi(pqp_batch* h, int64_t first, int64_t count, int64_t n_dir, const double* dH, const double* dg,
+                            const double* dA, const double* db, const double* dC, const double* dl, const double* du,
+                            int shared_mask, double eps, double rho, double mu, double* out, int32_t* active, double* rhs);
+/* ... on the `count` QPs idx[0..count): slot i of the tangent arrays / out / active / rhs belongs to QP idx[i]; an index
+ * listed twice: PQP_ERR_INVALID_ARGUMENT */
+int pqp_batch_tangent_multi_subset(pqp_batch* h, const int64_t* idx, int64_t count, int64_t n_dir, const double* dH,
+                                   const double* dg, const double* dA, const double* db, const double* dC, const double* dl,
+                                   const double* du, int shared_mask, double eps, double rho, double mu, double* out,
+                                   int32_t* active, double* rhs);
 /* The backward pass of QPs WITH box constraints (a handle created with box_constraints = 1; the entries above answer
  * PQP_ERR_UNSUPPORTED for one).  The constraint list is [C; I]: n_c = n_in + dim rows, z = [z_in; z_box], and
  * compute_backward + compute_backward_loss_ESG run over those rows in that order (the scaling vector of the inequality

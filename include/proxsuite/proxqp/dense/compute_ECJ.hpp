@@ -3,7 +3,8 @@
 // qp.model.backward_data.  Same signature and defaults as the reference
 // (include/proxsuite/proxqp/dense/compute_ECJ.hpp:29-132); the work is one launch of
 // pqp_backward_kernel through pqp_batch_backward_range (include/proxqp_hip.h).  compute_backward_multi /
-// solution_jacobians: K loss derivatives of one QP in one launch (pqp_batch_backward_multi).
+// solution_jacobians: K loss derivatives of one QP in one launch (pqp_batch_backward_multi).  compute_forward_sensitivity:
+// the opposite direction, tangents of (x, y, z) for K tangents of the parameters (pqp_batch_tangent_multi).
 // A QP with box constraints (is_box_constrained()) goes through pqp_batch_backward_box: its constraint list is [C; I], a
 // loss derivative has dim + n_eq + n_in + dim entries (dL/dx | dL/dy | dL/dz_in | dL/dz_box), and backward_data also
 // receives dL_dl_box / dL_du_box.
@@ -144,6 +145,56 @@ solution_jacobians(QP<T>& solved_qp, T eps = 1.E-4, T rho_new = 1.E-6, T mu_new 
     }
   }
   return J;
+}
+
+// Tangents of the parameters of one QP, K = n_dir directions: every array is optional (null: a zero tangent), row-major,
+// direction-major -- dH [K][dim][dim] (need not be symmetric: its symmetric part acts), dg [K][dim], dA [K][n_eq][dim],
+// db [K][n_eq], dC [K][n_in][dim], dl / du [K][n_in].
+template<typename T>
+struct Tangents
+{
+  const T *dH = nullptr, *dg = nullptr, *dA = nullptr, *db = nullptr, *dC = nullptr, *dl = nullptr, *du = nullptr;
+  isize n_dir = 1;
+};
+
+// K x dim, K x n_eq, K x n_in (inactive rows of dz are 0) and the n_in flags (bit 0: active from above, bit 1: from below)
+template<typename T>
+struct ForwardSensitivity
+{
+  Mat<T> dx, dy, dz;
+  std::vector<std::int32_t> active;
+};
+
+// Forward-mode sensitivities of a solved QP (pqp_batch_tangent_multi, the adjoint of compute_backward): by how much
+// (x, y, z) move when the parameters move by `tangents`, one refined KKT solve per direction on one factorisation at
+// (rho_new, mu_new).  qp.model.backward_data is left alone.  A QP with box constraints throws (no box tangents).
+template<typename T>
+ForwardSensitivity<T>
+compute_forward_sensitivity(QP<T>& solved_qp, const Tangents<T>& tangents, T eps = 1.E-4, T rho_new = 1.E-6, T mu_new = 1.E-6)
+{
+  const isize n = solved_qp.model.dim, ne = solved_qp.model.n_eq, ni = solved_qp.model.n_in, ntot = n + ne + ni;
+  const isize K = tangents.n_dir;
+  if (K < 0)
+    detail::bad_size("the number of directions is not negative.", K, 0);
+  Mat<T> out(K, ntot);
+  ForwardSensitivity<T> r{ Mat<T>(K, n), Mat<T>(K, ne), Mat<T>(K, ni), std::vector<std::int32_t>(usize(ni), 0) };
+  if (K == 0)
+    return r;
+  detail::PoolLock lock(solved_qp.pool()->mtx);
+  solved_qp.push_settings();
+  detail::check(pqp_batch_tangent_multi(solved_qp.pool()->h, solved_qp.slot(), 1, K, tangents.dH, tangents.dg, tangents.dA,
+                                        tangents.db, tangents.dC, tangents.dl, tangents.du, 0, eps, rho_new, mu_new, out.data(),
+                                        r.active.data(), nullptr));
+  solved_qp.pull(); // results.info carries the backward proximal parameters, as after compute_backward
+  for (isize k = 0; k < K; ++k) {
+    for (isize i = 0; i < n; ++i)
+      r.dx(k, i) = out(k, i);
+    for (isize i = 0; i < ne; ++i)
+      r.dy(k, i) = out(k, n + i);
+    for (isize i = 0; i < ni; ++i)
+      r.dz(k, i) = out(k, n + ne + i);
+  }
+  return r;
 }
 
 } // namespace dense

@@ -52,7 +52,7 @@ def build_randqp(force: bool = False) -> Path:
 # pqp_kernels.hip is compiled once per kernel family (see its header): every solve kernel is
 # ~350 KB of inlined code and takes about a minute of hipcc time, so the objects are built in
 # parallel and linked into one shared library.
-KERNEL_TUS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25)
+KERNEL_TUS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27)
 # families outside the solver (19: the eigenvalue estimates of pqp_eig.hpp): built and linked like the others, their
 # resources frozen in a record of their own (tests/golden/eig_kernel_resources_expected.json) -- the solver's frozen record
 # names the solver's kernels and no others
@@ -66,7 +66,10 @@ AUXILIARY_TUS = (19,)
 # jacobians (tests/golden/bwbox_kernel_resources_expected.json, written by --freeze under the name below)
 # 25, batches that share a model: the broadcast of one model array to the QPs of a range and the ordered sum of a per-QP
 # array (csrc/pqp_shared.hpp, tests/golden/shared_model_kernel_resources_expected.json)
-NAMED_TUS = {"backward_multi": (20, 21), "infeas_backward": (22,), "backward_box": (23, 24), "shared_model": (25,)}
+# 26 / 27, forward-mode sensitivities: the K-tangent solve in LDS and on an HBM slice, and the assembly of its right-hand
+# sides from the parameter tangents (csrc/pqp_tangent.hpp, tests/golden/tangent_kernel_resources_expected.json)
+NAMED_TUS = {"backward_multi": (20, 21), "infeas_backward": (22,), "backward_box": (23, 24), "shared_model": (25,),
+             "tangent": (26, 27)}
 # (the frozen record of a group is <RECORD_NAMES.get(group, group)>_kernel_resources_expected.json)
 RECORD_NAMES = {"backward_box": "bwbox"}
 OBJ_DIR = ROOT / "build" / "obj"
@@ -187,7 +190,9 @@ def build_hip(force: bool = False, extra_flags=(), out: Path = None, tus=KERNEL_
     # (pqp_eig.hpp: family 19 alone includes it; pqp_capi.hip reads its host half)
     # (pqp_shared.hpp: family 25 alone includes it; pqp_capi.hip reads its constants)
     only = {"pqp_dwave.hpp": ("kernels_17.o", "kernels_6.o"), "pqp_eig.hpp": ("kernels_19.o", "capi.o"),
-            "pqp_shared.hpp": ("kernels_25.o", "capi.o")}
+            "pqp_shared.hpp": ("kernels_25.o", "capi.o"),
+            # (pqp_tangent.hpp: families 26 and 27 alone include it; pqp_capi.hip reads its argument records)
+            "pqp_tangent.hpp": ("kernels_26.o", "kernels_27.o", "capi.o")}
     def deps_of(o):
         return [h for h in common if h.name not in only or o.name in only[h.name]] + [CSRC / HOST_OBJECTS.get(o.name, "pqp_kernels.hip")]
     def compile_object(o):

@@ -66,7 +66,8 @@ class NativeLib:
                "pqp_multi_update_eig", "pqp_estimate_min_eigenvalues", "pqp_batch_backward_multi",
                "pqp_batch_backward_multi_subset", "pqp_batch_backward_closest_feasible", "pqp_batch_backward_box",
                "pqp_batch_backward_box_subset", "pqp_batch_get_backward_box", "pqp_batch_init_shared",
-               "pqp_batch_update_shared", "pqp_batch_get_backward_sum", "pqp_multi_init_shared", "pqp_multi_update_shared")
+               "pqp_batch_update_shared", "pqp_batch_get_backward_sum", "pqp_multi_init_shared", "pqp_multi_update_shared",
+               "pqp_batch_tangent_multi", "pqp_batch_tangent_multi_subset")
 
     def __init__(self, path, legacy=False):
         """legacy=True (A/B scripts only): an older build of the library that lacks the newer entries can still be
@@ -127,6 +128,9 @@ class NativeLib:
         L.pqp_batch_backward_multi.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, _DP] + [C.c_double] * 3 + [_DP, C.POINTER(C.c_int32)]
         L.pqp_batch_backward_multi_subset.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64, C.c_int64, _DP] + [C.c_double] * 3 + \
             [_DP, C.POINTER(C.c_int32)]
+        tangent_tail = [C.c_int64] + [_DP] * 7 + [C.c_int] + [C.c_double] * 3 + [_DP, C.POINTER(C.c_int32), _DP]
+        L.pqp_batch_tangent_multi.argtypes = [vp, C.c_int64, C.c_int64] + tangent_tail
+        L.pqp_batch_tangent_multi_subset.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64] + tangent_tail
         L.pqp_batch_backward_box.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, _DP] + [C.c_double] * 3 + [_DP, C.POINTER(C.c_int32)]
         L.pqp_batch_backward_box_subset.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64, C.c_int64, _DP] + [C.c_double] * 3 + \
             [_DP, C.POINTER(C.c_int32)]
@@ -635,6 +639,88 @@ class Batch:
         else:
             self.lib.check(self.lib.L.pqp_batch_backward_multi(self._h, int(first), rows, *args))
         return V, act
+
+    _TANGENT_NAMES = ("H", "g", "A", "b", "C", "l", "u")  # (bit k of a shared mask: PQP_SHARED_H ... PQP_SHARED_U)
+
+    def tangent_multi(self, eps=1e-4, rho=1e-6, mu=1e-6, dH=None, dg=None, dA=None, db=None, dC=None, dl=None, du=None,
+                      shared=(), first=None, count=None, idx=None, into=None, rhs=None, n_dir=None):
+        """pqp_batch_tangent_multi(_subset): forward-mode sensitivities of the solved QPs, K directions per QP on one
+        factorisation.  A tangent is [rows, K, ...] with the trailing shape of one QP's model array (numpy or torch, host
+        or ROCm; all of one kind), or [K, ...] when its name ("H", "g", "A", "b", "C", "l", "u") is listed in `shared`
+        (an int is taken as the mask of PQP_SHARED_* bits): one block for every QP.  None is a zero tangent.  rows = B,
+        or `count` from `first`, or len(idx) (slot i belongs to QP idx[i]).  K is read off the arrays (`n_dir` when there
+        are none).  Returns (T, active) where the inputs live: T [rows, K, n + n_eq + n_in] = (T_x, T_y, T_z), active
+        [rows, n_in] int32 (bit 0: active from above, bit 1: from below).  `into=(T, active)` fills the caller's buffers;
+        `rhs` (a buffer shaped like T) receives (r_x | r_y | dC x)."""
+        n, ne, ni = self.n, self.n_eq, self.n_in
+        ntot = n + ne + ni
+        ii = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64)
+        if ii is not None:
+            first, rows = 0, len(ii)
+        elif first is None:
+            first, rows = 0, self.B
+        else:
+            rows = int(1 if count is None else count)
+        if isinstance(shared, int):
+            mask = int(shared)
+        else:
+            mask = 0
+            for name in shared:
+                mask |= 1 << self._TANGENT_NAMES.index(name)
+        given = (dH, dg, dA, db, dC, dl, du)
+        tails = ((n, n), (n,), (ne, n), (ne,), (ni, n), (ni,), (ni,))
+        is_torch = any(hasattr(t, "data_ptr") for t in given if t is not None)
+        if is_torch:
+            import torch
+        K, device, arrs = (None if n_dir is None else int(n_dir)), None, []
+        for k, (t, tail) in enumerate(zip(given, tails)):
+            if t is None:
+                arrs.append(None)
+                continue
+            if is_torch:
+                if not hasattr(t, "data_ptr"):
+                    raise ValueError("tangent_multi: the tangents must all be numpy arrays or all be torch tensors")
+                a = t.detach()
+                if a.dtype != torch.float64 or not a.is_contiguous():
+                    a = a.to(torch.float64).contiguous()
+                if device is not None and a.device != device:
+                    raise ValueError("tangent_multi: the tangents must live on one device")
+                device = a.device
+            else:
+                a = np.ascontiguousarray(np.asarray(t, dtype=np.float64))
+            lead = () if (mask >> k) & 1 else (rows,)
+            K = int(a.shape[len(lead)]) if K is None and len(a.shape) == len(lead) + 1 + len(tail) else K
+            if tuple(a.shape) != lead + (K,) + tail:
+                raise ValueError("wrong argument size: d%s has shape %s, expected %s"
+                                 % (self._TANGENT_NAMES[k], tuple(a.shape), lead + ("K" if K is None else K,) + tail))
+            arrs.append(a)
+        K = 1 if K is None else K
+        if into is not None:
+            T, act = into
+            is_torch = hasattr(T, "data_ptr") if not any(a is not None for a in arrs) else is_torch
+            if is_torch and device is None:
+                device = T.device
+        elif is_torch:
+            T = torch.zeros((rows, K, ntot), dtype=torch.float64, device=device)
+            act = torch.zeros((rows, ni), dtype=torch.int32, device=device)
+        else:
+            T, act = np.zeros((rows, K, ntot)), np.zeros((rows, ni), dtype=np.int32)
+        bufs = [("T", T, (rows, K, ntot)), ("active", act, (rows, ni))] + ([("rhs", rhs, (rows, K, ntot))] if rhs is not None else [])
+        for name, buf, shape in bufs:
+            ok = (buf.is_contiguous() if hasattr(buf, "data_ptr") else buf.flags["C_CONTIGUOUS"]) and tuple(buf.shape) == shape
+            if not ok or hasattr(buf, "data_ptr") != is_torch or (is_torch and buf.device != device):
+                raise ValueError("tangent_multi: %s must be contiguous, of shape %s and live where the tangents live" % (name, shape))
+        if is_torch and device.type == "cuda":
+            torch.cuda.current_stream(device).synchronize()  # (the entry runs on the handle's stream and is synchronous)
+        ptr = (lambda t: t.data_ptr()) if is_torch else (lambda a: a.ctypes.data)
+        dp = lambda a: None if a is None else C.cast(ptr(a), _DP)
+        args = (K, *[dp(a) for a in arrs], mask, float(eps), float(rho), float(mu), dp(T),
+                C.cast(ptr(act), C.POINTER(C.c_int32)), dp(rhs))
+        if ii is not None:
+            self.lib.check(self.lib.L.pqp_batch_tangent_multi_subset(self._h, ii.ctypes.data_as(C.POINTER(C.c_int64)), rows, *args))
+        else:
+            self.lib.check(self.lib.L.pqp_batch_tangent_multi(self._h, int(first), rows, *args))
+        return T, act
 
     def backward_box(self, loss_derivatives, eps=1e-4, rho_backward=1e-6, mu_backward=1e-6, first=None, count=None,
                      idx=None, into=None):

@@ -17,6 +17,7 @@
 #include "pqp_diag.hpp"
 #include "pqp_eig.hpp"
 #include "pqp_shared.hpp"
+#include "pqp_tangent.hpp"
 
 namespace {
 
@@ -1397,10 +1398,10 @@ pqp_batch_copy_qp(pqp_batch* dst, int64_t dst_idx, pqp_batch* src, int64_t src_i
 }
 
 // What every backward entry checks before it touches the device, in this order: the handle, the subset list (`order`
-// receives it) or the range, box constraints, the loss derivatives.
+// receives it) or the range, box constraints, the loss derivatives (`ld_required` false: the tangent entries, which have none).
 static int
 backward_check(pqp_batch* h, int64_t first, int64_t count, const int64_t* idx, const double* loss_derivatives,
-               std::vector<int>& order)
+               std::vector<int>& order, bool ld_required = true)
 {
   if (!h)
     return fail(PQP_ERR_INVALID_ARGUMENT, "null batch handle");
@@ -1422,7 +1423,7 @@ backward_check(pqp_batch* h, int64_t first, int64_t count, const int64_t* idx, c
   if (h->dev.d.box)
     return fail(PQP_ERR_UNSUPPORTED, "compute_backward is defined for QPs without box constraints "
                                      "(reference dense/compute_ECJ.hpp ignores them)");
-  if (!loss_derivatives)
+  if (ld_required && !loss_derivatives)
     return fail(PQP_ERR_INVALID_ARGUMENT, "loss_derivatives is required");
   return PQP_OK;
 }
@@ -1622,6 +1623,143 @@ pqp_batch_backward_multi_subset(pqp_batch* h, const int64_t* idx, int64_t count,
   if (!h || (count > 0 && !idx))
     return fail(PQP_ERR_INVALID_ARGUMENT, "null argument");
   return backward_multi_impl(h, 0, count, idx, n_rhs, loss_derivatives, eps, rho_backward, mu_backward, out, active);
+}
+
+// pqp_batch_tangent_multi / _subset: the checks, the staging and the state rules of backward_multi_impl; two launches
+// (the right-hand sides R from the tangent arrays, then the K-tangent solve) on the handle's stream
+static int
+tangent_multi_impl(pqp_batch* h, int64_t first, int64_t count, const int64_t* idx, int64_t n_dir, const double* dH,
+                   const double* dg, const double* dA, const double* db, const double* dC, const double* dl,
+                   const double* du, int shared_mask, double eps, double rho, double mu, double* out, int32_t* active,
+                   double* rhs)
+{
+  std::vector<int> order;
+  if (int rc = backward_check(h, first, count, idx, nullptr, order, false))
+    return rc;
+  if (!out)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "out is required");
+  if (n_dir < 0)
+    return fail(PQP_ERR_INVALID_ARGUMENT, "n_dir is negative");
+  const pqp::Dims& d = h->dev.d;
+  const size_t n = size_t(d.n), ne = size_t(d.n_eq), ni = size_t(d.n_in), ntot = n + ne + ni;
+  // count * n_dir * (the largest tangent array of one QP and direction) doubles must be addressable, and the assembly
+  // kernel runs one workgroup per (QP, direction)
+  const size_t widest = std::max(ntot, n * std::max(n, std::max(ne, ni)));
+  const size_t lim = std::numeric_limits<int64_t>::max() / sizeof(double);
+  if (count > 0 && n_dir > 0 &&
+      (size_t(n_dir) > lim / size_t(count) || size_t(count) * size_t(n_dir) > lim / widest ||
+       size_t(count) * size_t(n_dir) > size_t(std::numeric_limits<int>::max())))
+    return fail(PQP_ERR_INVALID_ARGUMENT, "count * n_dir * (size of a tangent) overflows");
+  if (count == 0 || n_dir == 0)
+    return PQP_OK;
+  if (int rc = settle(h))
+    return rc;
+  PQP_ON_DEVICE(h->device);
+  if (int rc = backward_ready(h, first, count, idx))
+    return rc;
+  const size_t K = size_t(n_dir), total = size_t(count) * K * ntot, nflags = size_t(count) * ni;
+  // host arrays are staged through buffers of the handle (the tangents packed one behind the other in tg_stage); device
+  // (or pinned / managed) memory is used in place
+  const double* src[7] = { dH, dg, dA, db, dC, dl, du };
+  const size_t per_dir[7] = { n * n, n, ne * n, ne, ni * n, ni, ni };
+  static const int bit[7] = { PQP_SHARED_H, PQP_SHARED_G, PQP_SHARED_A, PQP_SHARED_B, PQP_SHARED_C, PQP_SHARED_L, PQP_SHARED_U };
+  size_t len[7], off[7], staged = 0;
+  bool in_place[7];
+  for (int t = 0; t < 7; ++t) {
+    len[t] = ((shared_mask & bit[t]) ? size_t(1) : size_t(count)) * K * per_dir[t];
+    if (len[t] == 0)
+      src[t] = nullptr; // (an array of no elements is a zero tangent)
+    in_place[t] = !src[t] || pqp_device_readable(src[t]);
+    off[t] = staged;
+    if (!in_place[t])
+      staged += len[t];
+  }
+  const bool out_in_place = pqp_device_readable(out), rhs_in_place = rhs && pqp_device_readable(rhs);
+  const bool active_in_place = !active || pqp_device_readable(active);
+  int rc = 0;
+  if (staged && (rc = grow(h, &h->tg_stage, &h->tg_stage_cap, staged)))
+    return rc;
+  const double* dev[7];
+  for (int t = 0; t < 7; ++t) {
+    dev[t] = src[t];
+    if (!in_place[t]) {
+      HIP_TRY(hipMemcpy(h->tg_stage + off[t], src[t], len[t] * sizeof(double), hipMemcpyHostToDevice));
+      dev[t] = h->tg_stage + off[t];
+    }
+  }
+  if (!rhs_in_place && (rc = grow(h, &h->tg_rhs, &h->tg_rhs_cap, total)))
+    return rc;
+  if (!out_in_place && (rc = grow(h, &h->bwm_out, &h->bwm_out_cap, total)))
+    return rc;
+  if (!active_in_place && (rc = grow(h, &h->bwm_active, &h->bwm_active_cap, nflags)))
+    return rc;
+  if ((rc = upload_settings(h)))
+    return rc;
+  pqp::TangentRhsArgs a{};
+  a.dH = dev[0];
+  a.dg = dev[1];
+  a.dA = dev[2];
+  a.db = dev[3];
+  a.dC = dev[4];
+  a.shared_mask = shared_mask;
+  a.R = rhs_in_place ? rhs : h->tg_rhs;
+  a.n_dir = long(n_dir);
+  a.first = long(first);
+  a.order = nullptr;
+  pqp::TangentArgs m{};
+  m.R = a.R;
+  m.dl = dev[5];
+  m.du = dev[6];
+  m.dl_stride = (shared_mask & PQP_SHARED_L) ? 0 : long(K * ni);
+  m.du_stride = (shared_mask & PQP_SHARED_U) ? 0 : long(K * ni);
+  m.eps = eps;
+  m.rho_new = rho;
+  m.mu_new = mu;
+  m.out = out_in_place ? out : h->bwm_out;
+  m.active = active ? (active_in_place ? reinterpret_cast<int*>(active) : h->bwm_active) : nullptr;
+  m.n_dir = long(n_dir);
+  m.first = long(first);
+  m.order = nullptr;
+  if (idx) {
+    HIP_TRY(hipMemcpy(h->d_order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
+    h->order_valid = false;
+    a.order = m.order = h->d_order;
+  }
+  // (the epilogue rewrites Info of every QP of the launch: a host mirror of it no longer holds what the device holds)
+  for (int64_t i = 0; i < count; ++i)
+    mirror_stale(h, idx ? idx[i] : first + i);
+  if ((rc = pqp_launch_tangent_rhs(h, a, long(count))))
+    return rc;
+  if ((rc = h->vec_scratch ? pqp_launch_tangent_multi_hbm(h, m, long(count)) : pqp_launch_tangent_multi(h, m, long(count))))
+    return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (!out_in_place)
+    HIP_TRY(hipMemcpy(out, h->bwm_out, total * sizeof(double), hipMemcpyDeviceToHost));
+  if (rhs && !rhs_in_place)
+    HIP_TRY(hipMemcpy(rhs, h->tg_rhs, total * sizeof(double), hipMemcpyDeviceToHost));
+  if (!active_in_place && nflags)
+    HIP_TRY(hipMemcpy(active, h->bwm_active, nflags * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return PQP_OK;
+}
+
+int
+pqp_batch_tangent_multi(pqp_batch* h, int64_t first, int64_t count, int64_t n_dir, const double* dH, const double* dg,
+                        const double* dA, const double* db, const double* dC, const double* dl, const double* du,
+                        int shared_mask, double eps, double rho, double mu, double* out, int32_t* active, double* rhs)
+{
+  return tangent_multi_impl(h, first, count, nullptr, n_dir, dH, dg, dA, db, dC, dl, du, shared_mask, eps, rho, mu, out, active,
+                            rhs);
+}
+
+int
+pqp_batch_tangent_multi_subset(pqp_batch* h, const int64_t* idx, int64_t count, int64_t n_dir, const double* dH,
+                               const double* dg, const double* dA, const double* db, const double* dC, const double* dl,
+                               const double* du, int shared_mask, double eps, double rho, double mu, double* out,
+                               int32_t* active, double* rhs)
+{
+  if (!h || (count > 0 && !idx))
+    return fail(PQP_ERR_INVALID_ARGUMENT, "null argument");
+  return tangent_multi_impl(h, 0, count, idx, n_dir, dH, dg, dA, db, dC, dl, du, shared_mask, eps, rho, mu, out, active, rhs);
 }
 
 // pqp_batch_backward_box / _subset: backward_multi_impl for a box handle, rows and flags over the n_in + n rows of [C; I];

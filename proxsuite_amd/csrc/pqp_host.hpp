@@ -130,6 +130,11 @@ struct pqp_batch
   // result of pqp_batch_get_backward_sum (sized on first use)
   double *shared_stage = nullptr, *sum_partial = nullptr;
   size_t shared_stage_cap = 0, sum_partial_cap = 0;
+  // pqp_batch_tangent_multi (pqp_tangent.hpp; grow-only, *_cap in elements): the host tangent arrays of a call, packed one
+  // behind the other, and the right-hand sides R of the launch when the caller does not hand a device buffer for them
+  // (host `out` / `active` go through bwm_out / bwm_active)
+  double *tg_stage = nullptr, *tg_rhs = nullptr;
+  size_t tg_stage_cap = 0, tg_rhs_cap = 0;
   // Longest-processing-time-first dispatch (OFF by default, pqp_batch_set_schedule): after a
   // whole-batch solve the per-QP device cycle counts order the NEXT whole-batch solve of the same
   // handle, most expensive QP first.  QPs are independent, so the order changes nothing but the

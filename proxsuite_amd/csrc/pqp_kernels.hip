@@ -27,7 +27,7 @@
 //                                     workgroup barrier orders global accesses within a workgroup as it
 //                                     does LDS ones).  Slow per QP -- every vector access is an L1/L2 round
 //                                     trip -- but it removes the size ceiling below 1024 rows.
-#if PQP_TU == 9 || PQP_TU == 21 || PQP_TU == 24
+#if PQP_TU == 9 || PQP_TU == 21 || PQP_TU == 24 || PQP_TU == 27
 #define PQP_VECTORS_IN_HBM 1
 #define PQP_LDS __attribute__((address_space(1)))
 #define PQP_GLOBAL __attribute__((address_space(1)))
@@ -38,7 +38,7 @@
 #endif
 // the translation units whose kernels run at 128 VGPRs per lane keep 4 instead of 8 MFMA k-steps of
 // operand loads in flight in the Z / G build (+2 % at C2 and C4, profiles/r02_ab_compiler_flags.txt)
-#if (PQP_TU == 1 || PQP_TU == 4 || PQP_TU == 8 || PQP_TU == 9 || PQP_TU == 21 || PQP_TU == 24) && !defined(PQP_ZG_DEPTH)
+#if (PQP_TU == 1 || PQP_TU == 4 || PQP_TU == 8 || PQP_TU == 9 || PQP_TU == 21 || PQP_TU == 24 || PQP_TU == 27) && !defined(PQP_ZG_DEPTH)
 #define PQP_ZG_DEPTH 4
 #endif
 // (the one-wavefront diagonal kernel is not short of scalar registers: its per-QP pointers are ordinary values -- the
@@ -68,6 +68,10 @@
 //  25  pqp_broadcast_kernel<256>     batches that share a model (pqp_shared.hpp): one model array written to every QP of a range
 //                                     (pqp_batch_init_shared / pqp_batch_update_shared), and pqp_sum_kernel<256>, the sum of a
 //                                     per-QP array over a range in a fixed order (pqp_batch_get_backward_sum)
+//  26  pqp_tangent_multi_kernel<.>   forward-mode sensitivities (pqp_tangent.hpp): K tangents of (x, y, z) per QP on one
+//                                     factorisation; and pqp_tangent_rhs_kernel<256>, which forms their right-hand sides
+//                                     from the parameter tangents (each tangent matrix read once)
+//  27  pqp_tangent_multi_hbm_kernel<1024>  the same on a slice of the HBM scratch buffer per workgroup (as 9, 21 and 24)
 #if PQP_TU == 0 || PQP_TU == 22
 #define PQP_INFEAS_DEVICE 1 // (pqp_host.hpp includes pqp_infeas.hpp for the launchers' argument record: the kernels' bodies with it here)
 #endif
@@ -81,6 +85,11 @@
 #if PQP_TU == 0 || PQP_TU == 25
 #define PQP_SHARED_DEVICE 1
 #include "pqp_shared.hpp"
+#endif
+
+#if PQP_TU == 0 || PQP_TU == 26 || PQP_TU == 27
+#define PQP_TANGENT_DEVICE 1
+#include "pqp_tangent.hpp"
 #endif
 
 #define PQP_TU_HAS(k) (PQP_TU == 0 || PQP_TU == (k))
@@ -591,6 +600,81 @@ int
 pqp_launch_bwbox_hbm(pqp_batch* h, const pqp::BackwardMultiArgs& bw, long count)
 {
   hipLaunchKernelGGL((pqp_bwbox_hbm_kernel<1024>), dim3((unsigned)count), dim3(1024), 0, h->stream, h->dev, bw,
+                     h->vec_scratch, (long)((h->lds_solve + 7) / 8));
+  HIP_TRY(hipGetLastError());
+  return PQP_OK;
+}
+#endif
+
+#if PQP_TU_HAS(26)
+template<int NT>
+__global__ __launch_bounds__(NT) void
+pqp_tangent_rhs_kernel(pqp::Batch batch, pqp::TangentRhsArgs a)
+{
+  HIP_DYNAMIC_SHARED(double, smem)
+  pqp::tangent_rhs_body<NT>(batch, a, smem);
+}
+
+// R[slot][k][:] of every QP of the launch and every direction: workgroup slot * n_dir + k
+int
+pqp_launch_tangent_rhs(pqp_batch* h, const pqp::TangentRhsArgs& a, long count)
+{
+  const size_t lds = pqp::tangent_rhs_lds_bytes(h->dev.d.n, h->dev.d.n_eq, h->dev.d.n_in, 256);
+  if (lds > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&pqp_tangent_rhs_kernel<256>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((pqp_tangent_rhs_kernel<256>), dim3((unsigned)(count * a.n_dir)), dim3(256), lds, h->stream, h->dev, a);
+  HIP_TRY(hipGetLastError());
+  return PQP_OK;
+}
+
+template<int NT>
+__global__ __launch_bounds__(NT, 2) void
+pqp_tangent_multi_kernel(pqp::Batch batch, pqp::TangentArgs tg)
+{
+  HIP_DYNAMIC_SHARED(double, smem)
+  pqp::tangent_multi_body<NT>(batch, tg, (long)blockIdx.x, (pqp::lptr)smem);
+}
+
+template<int NT>
+static int
+launch_tangent_multi(pqp_batch* h, const pqp::TangentArgs& tg, long count)
+{
+  if (h->lds_solve > 64 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&pqp_tangent_multi_kernel<NT>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_solve));
+  hipLaunchKernelGGL((pqp_tangent_multi_kernel<NT>), dim3((unsigned)count), dim3(NT), h->lds_solve, h->stream, h->dev, tg);
+  HIP_TRY(hipGetLastError());
+  return PQP_OK;
+}
+
+int
+pqp_launch_tangent_multi(pqp_batch* h, const pqp::TangentArgs& tg, long count)
+{
+  switch (h->nt) {
+    case 256:
+      return launch_tangent_multi<256>(h, tg, count);
+    case 512:
+      return launch_tangent_multi<512>(h, tg, count);
+    default:
+      return launch_tangent_multi<1024>(h, tg, count);
+  }
+}
+#endif
+
+#if PQP_TU == 27 || (PQP_TU == 0 && defined(PQP_EMULATED_MFMA))
+// (as pqp_backward_multi_hbm_kernel: workgroup i works on the i-th slice of the handle's scratch buffer; no dynamic LDS)
+template<int NT>
+__global__ __launch_bounds__(NT, PQP_WPS_1024) void
+pqp_tangent_multi_hbm_kernel(pqp::Batch batch, pqp::TangentArgs tg, double* scratch, long stride)
+{
+  pqp::tangent_multi_body<NT>(batch, tg, (long)blockIdx.x, (pqp::lptr)(scratch + (long)blockIdx.x * stride));
+}
+
+int
+pqp_launch_tangent_multi_hbm(pqp_batch* h, const pqp::TangentArgs& tg, long count)
+{
+  hipLaunchKernelGGL((pqp_tangent_multi_hbm_kernel<1024>), dim3((unsigned)count), dim3(1024), 0, h->stream, h->dev, tg,
                      h->vec_scratch, (long)((h->lds_solve + 7) / 8));
   HIP_TRY(hipGetLastError());
   return PQP_OK;

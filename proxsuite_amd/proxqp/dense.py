@@ -14,6 +14,7 @@ expose-parallel.hpp:27-46, expose-solve.hpp) for the dense ProxQP path:
     compute_backward_multi(qp, loss_derivatives[K, ntot], ...)              -> dict (K rows, one factorisation)
     compute_backward_closest_feasible(qp, loss_derivative, ...)             -> qp.model.backward_data (closest-feasible QPs)
     solution_jacobians(qp, ...)                                             -> dx_dg, dx_db, dx_du, dx_dl
+    compute_forward_sensitivity(qp, dH, dg, dA, db, dC, dl, du, ...)        -> dx, dy, dz, active (tangents; one factorisation)
     solve_backward_in_parallel(num_threads, qps, loss_derivatives, ...)
     estimate_minimal_eigen_value_of_symmetric_matrix(H, ...)               (host-side helper)
 
@@ -34,7 +35,7 @@ from .._ctypes_defs import (DenseBackend, EigenValueEstimateMethodOption, Hessia
                             MeritFunctionType, QPSolverOutput, pqp_info, pqp_settings)
 
 __all__ = ["QP", "BatchQP", "VectorQP", "VectorLossDerivatives", "solve_in_parallel", "solve", "solve_no_gil",
-           "compute_backward", "compute_backward_multi", "compute_backward_closest_feasible", "solution_jacobians", "solve_backward_in_parallel", "estimate_minimal_eigen_value_of_symmetric_matrix",
+           "compute_backward", "compute_backward_multi", "compute_backward_closest_feasible", "solution_jacobians", "compute_forward_sensitivity", "solve_backward_in_parallel", "estimate_minimal_eigen_value_of_symmetric_matrix",
            "EigenValueEstimateMethodOption", "DenseBackend", "HessianType", "InitialGuess",
            "QPSolverOutput", "MeritFunctionType", "Settings", "Results", "Info", "Model", "BackwardData"]
 
@@ -703,6 +704,38 @@ def solution_jacobians(qp, eps=1e-4, rho_backward=1e-6, mu_backward=1e-6):
     if qp.is_box_constrained():
         out["dx_dl_box"], out["dx_du_box"] = r["dL_dl_box"], r["dL_du_box"]
     return out
+
+
+def compute_forward_sensitivity(qp, dH=None, dg=None, dA=None, db=None, dC=None, dl=None, du=None, eps=1e-4, rho=1e-6,
+                                mu=1e-6):
+    """Forward-mode sensitivities of one solved QP (pqp_batch_tangent_multi): by how much (x, y, z) move when the
+    parameters move by (dH, dg, dA, db, dC, dl, du) -- the adjoint of compute_backward, one refined KKT solve per
+    direction on one factorisation at (rho, mu).  A tangent has the shape of the QP's own array (one direction) or a
+    leading dimension K (K directions; every given tangent then has it); None is a zero tangent; dH need not be symmetric
+    (its symmetric part acts).  Returns a dict dx [n], dy [n_eq], dz [n_in] ([K, ...] for K directions; inactive rows of
+    dz are 0) and `active` [n_in] (bit 0: active from above, bit 1: from below).  qp.model.backward_data is left alone.
+    QPs with box constraints are not served (ValueError)."""
+    if qp.is_box_constrained():
+        raise ValueError("compute_forward_sensitivity is defined for QPs without box constraints (pqp_batch_tangent_multi "
+                         "answers PQP_ERR_UNSUPPORTED for a handle that has them)")
+    batch = qp._pool.batch
+    n, ne, ni = batch.n, batch.n_eq, batch.n_in
+    base = dict(H=2, g=1, A=2, b=1, C=2, l=1, u=1)
+    given = dict(H=dH, g=dg, A=dA, b=db, C=dC, l=dl, u=du)
+    arrs, many = {}, None
+    for name, t in given.items():
+        if t is None:
+            continue
+        a = np.ascontiguousarray(np.asarray(t, dtype=np.float64))
+        if a.ndim not in (base[name], base[name] + 1) or (many is not None and many != (a.ndim > base[name])):
+            raise ValueError("wrong argument size: d%s has shape %s; the tangents take one direction (the QP's own shapes) "
+                             "or all carry a leading dimension K" % (name, a.shape))
+        many = a.ndim > base[name]
+        arrs["d" + name] = a[None] if many else a[None, None]
+    T, act = batch.tangent_multi(eps, rho, mu, first=qp._slot, count=1, **arrs)
+    qp._pool.touch()
+    T = T[0] if many else T[0, 0]
+    return dict(dx=T[..., :n].copy(), dy=T[..., n:n + ne].copy(), dz=T[..., n + ne:].copy(), active=act[0])
 
 
 def solve_backward_in_parallel(num_threads=None, qps=None, loss_derivatives=None, eps=1e-4, rho_backward=1e-6,

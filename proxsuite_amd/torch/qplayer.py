@@ -17,6 +17,11 @@ Parameters WITHOUT a batch dimension (2-D Q, A, G; 1-D vectors: a layer's weight
 they are: they go through ONE pqp_batch_init_shared, which gives them to every QP on the device, and their gradients are the
 per-QP jacobians summed on the device (pqp_batch_get_backward_sum, csrc/pqp_shared.hpp); no [B, ...] tensor is made for them.
 
+Forward mode: `solution_tangents` (one forward, one pqp_batch_tangent_multi call) and a `jvp` on the feasible layer's
+Function, so that torch.autograd.forward_ad works through QPFunction(structural_feasibility=True): the tangents of
+(x, y, z) for the tangents of the seven parameters, one refined KKT solve on the factorisation of the backward pass
+(csrc/pqp_tangent.hpp).  The closest-feasible layer and QPFunctionBox have no jvp.
+
 The closest-feasible variant (`structural_feasibility=False`) differentiates through its sparse backend in the
 reference (qplayer.py:371-610): per QP a rectangular linear system K w = r, solved as a QP with zero Hessian, K as
 equality constraints and primal_infeasibility_solving.  That QP is dense and of the kind this engine solves, so here the
@@ -188,10 +193,58 @@ def solution_jacobians(Q, p, A, b, G, l, u, eps=1e-9, maxIter=1000, eps_backward
             torch.where(up, -Vz, zero).to(t))
 
 
+def _tangents(batch, dev, shapes, batched, tangents, eps_backward, rho_backward, mu_backward):
+    """(dx, dy, dz) in fp64 for ONE direction.  shapes[i] / batched[i]: the shape of parameter i (() when it is absent) and
+    whether it carries the batch dimension; tangents[i] (None: zero) has that shape.  A parameter without batch dimension
+    is shared by the batch and its tangent goes in as it is, with its shared bit"""
+    B, n, ne, ni = batch.B, batch.n, batch.n_eq, batch.n_in
+    names = ("H", "g", "A", "b", "C", "l", "u")
+    args, shared = {}, []
+    for name, shape, bt, t in zip(names, shapes, batched, tangents):
+        if t is None or not len(shape):
+            continue
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("the tangent of %s has shape %s, its parameter %s" % (name, tuple(t.shape), tuple(shape)))
+        t = _dense64(t).to(dev)
+        if bt:
+            args["d" + name] = t.unsqueeze(1)  # [B, 1, ...]
+        else:
+            args["d" + name] = t.unsqueeze(0)  # [1, ...]: one block for every QP
+            shared.append(name)
+    if not args:
+        zero = lambda k: torch.zeros((B, k), dtype=torch.float64, device=dev)
+        return zero(n), zero(ne), zero(ni)
+    T, _ = batch.tangent_multi(eps_backward, rho_backward, mu_backward, shared=shared, **args)
+    return T[:, 0, :n].clone(), T[:, 0, n:n + ne].clone(), T[:, 0, n + ne:].clone()
+
+
+def _shapes_and_batched(params):
+    """what QPFunction keeps of its seven parameters: the shape (() for an absent one) and whether it carries the batch dimension"""
+    dims = (3, 2, 3, 2, 3, 2, 2)
+    return (tuple(tuple(t_.shape) if t_.numel() else () for t_ in params),
+            tuple(t_.ndimension() == d for t_, d in zip(params, dims)))
+
+
+def solution_tangents(Q, p, A, b, G, l, u, dQ=None, dp=None, dA=None, db=None, dG=None, dl=None, du=None, eps=1e-9,
+                      maxIter=1000, eps_backward=1.0e-4, rho_backward=1.0e-6, mu_backward=1.0e-6):
+    """The solution of a batch of QPs and its directional derivative: one forward solve with the settings of QPFunction,
+    then ONE tangent call (pqp_batch_tangent_multi).  A tangent has the shape of its parameter (a parameter without batch
+    dimension is shared by the batch, and so is its tangent); None is a zero tangent.  Returns (x, y, z, dx, dy, dz) on
+    the inputs' device, in the inputs' dtype."""
+    nbatch = _extract_nbatch((Q, 3), (p, 2), (A, 3), (b, 2), (G, 3), (l, 2), (u, 2))
+    lease, x, y, z, _, _ = _solve_batch(Q, p, A, b, G, l, u, eps, maxIter, infeasible=False, nbatch=nbatch)
+    shapes, batched = _shapes_and_batched((Q, p, A, b, G, l, u))
+    d = _tangents(lease.batch, Q.device, shapes, batched, (dQ, dp, dA, db, dG, dl, du), eps_backward, rho_backward,
+                  mu_backward)
+    t = Q.dtype
+    return (x.to(t), y.to(t), z.to(t)) + tuple(v.to(t) for v in d)
+
+
 def QPFunction(eps=1e-9, maxIter=1000, eps_backward=1.0e-4, rho_backward=1.0e-6, mu_backward=1.0e-6,
                omp_parallel=False, structural_feasibility=True):
     """Factory with the reference's signature (qplayer.py:12-20).  `omp_parallel` is accepted and
-    ignored: the batch is always solved in one launch."""
+    ignored: the batch is always solved in one launch.  The feasible layer (`structural_feasibility=True`) also has a
+    `jvp`: torch.autograd.forward_ad works through it.  The closest-feasible layer and QPFunctionBox have none."""
 
     class QPFunctionFn(Function):
         @staticmethod
@@ -207,6 +260,14 @@ def QPFunction(eps=1e-9, maxIter=1000, eps_backward=1.0e-4, rho_backward=1.0e-6,
             ctx.batched = (Q_.ndimension() == 3, p_.ndimension() == 2, A_.ndimension() == 3, b_.ndimension() == 2,
                            G_.ndimension() == 3, l_.ndimension() == 2, u_.ndimension() == 2)
             return x.to(Q_.dtype), y.to(Q_.dtype), z.to(Q_.dtype)
+
+        @staticmethod
+        def jvp(ctx, *tangents):
+            # forward mode (torch.autograd.forward_ad): one tangent call on the handle the forward left solved.  An input
+            # without a tangent arrives as None and reaches the library as a null pointer.  The call reads (x, y, z) and
+            # the scaled model and rewrites only what backward() rewrites, so a later backward() finds what it needs.
+            d = _tangents(ctx.batch, ctx.dev, ctx.shapes, ctx.batched, tangents, eps_backward, rho_backward, mu_backward)
+            return tuple(v.to(ctx.dtype) for v in d)
 
         @staticmethod
         def backward(ctx, dl_dzhat, dl_dlams, dl_dnus):
